@@ -92,7 +92,7 @@ def _dry_run(world):
 
 @pytest.mark.timeout(240)
 def test_bench_default_c_extra_at_8_gpus_is_configs4_shape():
-    """At N = 8 the default run's compaction extra is SURVEY.md section 8(d) config 5: 3 key ranges
+    """At N = 8 the default --full run's compaction extra is SURVEY.md section 8(d) config 5: 3 key ranges
     of 1 Mi input blocks per GPU, 12.7 GB of L0 input per GPU, ~100 GB on 8 (VERDICT round 4,
     missing item 3) -- shown by the launcher's dry run, 8 gloo ranks (no GPU)."""
     line = _dry_run(8)
