@@ -81,25 +81,42 @@ def fingerprint32(key: bytes) -> int:
     return lib().lsmblk_fingerprint32(key, len(key))
 
 
+def sst_files_into(blocks, blk_off, nblk, sst_blk, sst_ent, nsst, kv: batch.KVStream, files, files_cap, file_off,
+                   stats, stream=None):
+    """Whole SST files into a caller's buffer (files may be None with files_cap 0: the size
+    alone).  stats[1] = the bytes required; where that exceeds files_cap the stats carry
+    CAPACITY and nothing is written.  No host sync of the result: read stats after one."""
+    dev = batch._dev_index(blk_off)
+    batch._need(blk_off, torch.int64, "blk_off", dev, nblk + 1)
+    batch._need(sst_blk, torch.int32, "sst_blk", dev, nsst + 1)
+    batch._need(sst_ent, torch.int32, "sst_ent", dev, nsst + 1)
+    batch._need(file_off, torch.int64, "file_off", dev, nsst + 1)
+    batch._need(stats, torch.int64, "stats", dev, batch.STATS_WORDS)
+    if files is not None:
+        batch._need(files, torch.uint8, "files", dev, files_cap)
+    elif files_cap:
+        raise ValueError("files: missing tensor")
+    kv.check(dev, "kv")
+    c = kv._c()
+    batch._native("lsmblk_sst_files_batch", dev, stream, batch._ptr(blocks), blk_off.data_ptr(), nblk,
+                  sst_blk.data_ptr(), sst_ent.data_ptr(), nsst, ctypes.byref(c),
+                  files.data_ptr() if files is not None else None, files_cap, file_off.data_ptr(),
+                  stats.data_ptr(), batch._stream_ptr(stream, dev))
+
+
 def sst_files(blocks, blk_off, sst_blk, sst_ent, kv: batch.KVStream, stream=None):
     """Whole SST files for every SST (sst_blk / sst_ent: u32 tables of nsst+1) -> (files u8 tensor,
     file_off int64 tensor[nsst+1]); file s = files[file_off[s]:file_off[s+1]]."""
     dev = torch.device("cuda", batch._dev_index(blk_off))
     sst_blk, sst_ent = batch._u32_table(sst_blk, dev), batch._u32_table(sst_ent, dev)
     nsst, nblk = sst_blk.numel() - 1, blk_off.numel() - 1
-    batch._need(blk_off, torch.int64, "blk_off", dev.index, nblk + 1)
-    kv.check(dev.index, "kv")
     file_off = torch.zeros(nsst + 1, dtype=torch.int64, device=dev)
     stats = torch.zeros(batch.STATS_WORDS, dtype=torch.int64, device=dev)
     kb, _ = kv.byte_sizes()
     cap = int(blocks.numel()) + 8 * nblk + 2 * kb + 64 * nsst + 2 * kv.n + 1024
     for _ in range(2):
         files = batch._aligned_empty(cap, dev)
-        c = kv._c()
-        batch._native("lsmblk_sst_files_batch", dev.index, stream, batch._ptr(blocks), blk_off.data_ptr(), nblk,
-                      sst_blk.data_ptr(), sst_ent.data_ptr(), nsst, ctypes.byref(c),
-                      files.data_ptr(), cap, file_off.data_ptr(), stats.data_ptr(),
-                      batch._stream_ptr(stream, dev.index))
+        sst_files_into(blocks, blk_off, nblk, sst_blk, sst_ent, nsst, kv, files, cap, file_off, stats, stream)
         torch.cuda.synchronize(dev)
         st = batch._status(stats)
         if st == -3:

@@ -27,17 +27,22 @@ _SRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 _NAMES = ("kDecImg", "kDecMaxE", "kDecOut", "kEmitKCap", "kEmitICap", "kEmitMaxE", "kTile")
 
 
-def kernel_constants(path=_SRC):
-    """{name: value} of the dispatch constants, from their `constexpr uint32_t NAME = N;` lines."""
+def read_constants(path, names):
+    """{name: value} of `names`, from their `constexpr uint32_t NAME = N;` lines in `path`."""
     with open(path) as f:
         text = f.read()
     out = {}
-    for name in _NAMES:
+    for name in names:
         m = re.search(r"^constexpr\s+uint32_t\s+%s\s*=\s*(\d+)\s*;" % name, text, re.M)
         if not m:
             raise RuntimeError(f"{name}: no `constexpr uint32_t {name} = N;` in {path}")
         out[name] = int(m.group(1))
     return out
+
+
+def kernel_constants(path=_SRC):
+    """{name: value} of the dispatch constants of the decode and emit kernels."""
+    return read_constants(path, _NAMES)
 
 
 K = kernel_constants()

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+import sst_cases
 from lsm_amd import batch, synth
 from lsm_amd import sst as S
 from lsm_amd._lib import LsmBlkError
@@ -123,7 +124,10 @@ def test_gpu_flush_memtable_file_equals_oracle(n, bs):
     mt = S.MemTable()
     for k, t, v in puts:
         mt.put(k, t, v)
-    want = pyref.sst_file(pyref.memtable_flush(puts), bs)
+    flushed = pyref.memtable_flush(puts)
+    if n == 30000:
+        assert len(flushed) > sst_cases.max_lds_count(), "not on the global-atomics bloom path"
+    want = pyref.sst_file(flushed, bs)
     got = S.flush_memtable(mt, bs)
     assert got == want
 
