@@ -581,12 +581,16 @@ def merge_runs(kv: KVStream, run_start, stream=None, merge_mode=LSMBLK_MERGE_RUN
     return out
 
 
-def sst_rotation(kv: KVStream, block_size: int, target_sst_size: int, stream=None):
+def sst_rotation(kv: KVStream, block_size: int, target_sst_size: int, stream=None, sst_cap=None):
     """SST cut points of compact_generate_sst (reference src/compact.rs:278-289) over the stream
-    handed to SsTableBuilder::add -> u32 numpy array of SST first entries, then kv.n."""
+    handed to SsTableBuilder::add -> u32 numpy array of SST first entries, then kv.n.
+    sst_cap: slots of the start table (default kv.n + 2, which always fits); a stream of more than
+    sst_cap - 1 SSTs raises LSMBLK_E_CAPACITY."""
     dev = torch.device("cuda", _dev_index(kv.key_off))
     kv.check(dev.index, "kv")
-    cap = kv.n + 2
+    cap = kv.n + 2 if sst_cap is None else int(sst_cap)
+    if cap < 1:
+        raise ValueError("sst_rotation: sst_cap must be >= 1")
     starts = torch.zeros(cap, dtype=torch.int32, device=dev)
     stats = torch.zeros(STATS_WORDS, dtype=torch.int64, device=dev)
     c = kv._c()

@@ -1862,8 +1862,9 @@ __global__ void rot_chain_check_kernel(RotArgs a, uint32_t k) {
   if (threadIdx.x || *(volatile uint32_t*)a.chain_end) return;
   const uint64_t n = rot_n(a);
   const uint64_t last = (2ull << k) - 1;  // elements [0, 2^(k+1)) are computed now
-  // the array is full (rot_finish_kernel then decides whether the chain ended) or it ended
-  if (last >= a.sst_cap || a.starts[last] >= n) *a.chain_end = k + 1;
+  // the array is full (rot_finish_kernel then decides whether the chain ended) or it ended; full
+  // includes sst_cap == 2^(k+1), where `last` is the array's last slot
+  if (last + 1 >= a.sst_cap || a.starts[last] >= n) *a.chain_end = k + 1;
 }
 
 // The chain past its first 2^K elements (K doubling levels done, the last without its squaring;
