@@ -532,6 +532,112 @@ uint32_t lsmblk_fingerprint32(const uint8_t* key, size_t klen);
 /* Bloom::may_contain (src/table/bloom.rs:104-120) over a decoded filter, host. */
 int lsmblk_bloom_may_contain(const uint8_t* filter, size_t nbytes, uint32_t k, uint32_t h);
 
+/* ------------------------------------------------------------------ SST point lookups (device) */
+/* The read side's point read: key_within -> bloom.may_contain(fingerprint32(key))
+ * -> SsTable::find_block_idx -> read_block -> BlockIterator::create_and_seek_to_key, for batches of
+ * (sst, key, read_ts) lookups over SST files resident in device memory, laid out as
+ * lsmblk_sst_files_batch writes them: file s = files[file_off[s] .. file_off[s+1]).  `files` and
+ * `index` must be 16-byte aligned (LSMBLK_E_INVAL otherwise).  The files are opened once (lsmblk_sst_open_batch: descriptors and a block
+ * index in caller-provided device buffers), then any number of lookup batches run over them
+ * (lsmblk_sst_get_batch).
+ * Not part of these calls: the per-block CRC of read_block (src/table.rs:226-230) -- callers verify
+ * a loaded file with lsmblk_crc32_batch or lsmblk_decode_batch_ex(LSMBLK_DECODE_VERIFY_CRC) -- and
+ * merging results across SSTs or levels (the caller orders its candidate SSTs). */
+
+/* One opened SST (64 bytes).  Positions are absolute byte offsets in `files` unless noted. */
+typedef struct {
+  uint32_t blk0;          /* index of the SST's first record in the block index (its slots are reserved
+                             by the block count its BlockMeta section claims, also when the open fails) */
+  uint32_t nblk;          /* blocks; 0 after a failed open (lookups then report LSMBLK_GET_ABSENT) */
+  uint32_t meta_offset;   /* file-relative start of the BlockMeta section = end of the data section */
+  uint32_t bloom_len;     /* bytes of the bloom filter's bit array (without k and the CRC) */
+  uint64_t bloom_pos;     /* the bit array (= bloom_offset) */
+  uint64_t first_key_pos; /* first key of the first block (SsTable::first_key), in the BlockMeta section */
+  uint64_t last_key_pos;  /* last key of the last block (SsTable::last_key) */
+  uint32_t first_key_len;
+  uint32_t last_key_len;
+  uint64_t max_ts;        /* the BlockMeta section's max_ts */
+  uint32_t bloom_k;       /* probes per key (the byte after the bit array) */
+  uint32_t err;           /* LSMBLK_ERR_* flags of this SST's open; 0 = opened */
+} lsmblk_sst_desc;
+
+/* One block of an opened SST (32 bytes; record blk0 + b is the SST's block b).  img_hi / img_lo are
+ * the first key's leading 16 bytes as two big-endian integers (bytes 0..7, 8..15; a shorter key is
+ * padded with zero bytes): img(a) < img(b) implies a < b in key order, equal images decide nothing. */
+typedef struct {
+  uint64_t img_hi, img_lo;
+  uint32_t off;           /* file-relative start of the block */
+  uint32_t end;           /* file-relative end of the framed block: the next block's offset, or meta_offset
+                             (read_block, src/table.rs:215-220); the block's bytes are [off, end - 4) */
+  uint32_t key_pos;       /* file-relative position of the block's first key in the BlockMeta section */
+  uint32_t key_len;
+} lsmblk_sst_index;
+
+/* SsTable::open (src/table.rs:162-186) for nsst files: per SST the footer (bloom_offset = the last 4
+ * bytes, meta_offset = the 4 bytes before the bloom section), the CRC of the bloom section
+ * (bloom.rs:49-60) and of the BlockMeta section (table.rs:65-93), then the walk over the BlockMeta
+ * records -> desc[s] and index[desc[s].blk0 ..).  Every offset read from a file is checked against
+ * the file's bounds before it is used; per SST, desc[s].err holds
+ *   LSMBLK_ERR_MALFORMED  a footer or record points outside its file or section, block offsets do
+ *                         not increase, or the SST has no block (the reference unwrap()s and panics)
+ *   LSMBLK_ERR_CHECKSUM   a section's CRC does not match
+ * and the other SSTs of the batch still open.  stats: [0] SSTs opened  [1] index records reserved
+ * (the required index_cap on CAPACITY)  [2] the OR of every desc[s].err  [3] error flags of the
+ * call as a whole: CAPACITY (index_cap too small: no SST is opened; index may be NULL with
+ * index_cap 0 to ask for the size), MALFORMED (file_off decreases), OVERFLOW (over 2^32 - 1
+ * blocks).  desc: device lsmblk_sst_desc[nsst].  Asynchronous. */
+int lsmblk_sst_open_batch(lsmblk_ctx* ctx, const uint8_t* files, const uint64_t* file_off, uint32_t nsst,
+                          lsmblk_sst_desc* desc, lsmblk_sst_index* index, uint64_t index_cap, uint64_t* stats,
+                          void* stream);
+
+/* Result of one lookup (40 bytes). */
+typedef struct {
+  uint32_t status;   /* LSMBLK_GET_* */
+  uint32_t blk, ent; /* where SsTableIterator::seek_to_key_inner (src/table/iterator.rs:56-68) leaves the
+                        iterator: SST-local block and entry; blk == nblk (ent 0): it ended invalid;
+                        0xFFFFFFFF both: no seek was made */
+  uint32_t hit_blk, hit_ent; /* the visible version (FOUND, TOMBSTONE); else 0xFFFFFFFF */
+  uint32_t vlen;     /* its value's bytes */
+  uint64_t ts;       /* its timestamp */
+  uint64_t val_pos;  /* absolute offset of its value bytes in `files` */
+} lsmblk_get_result;
+
+#define LSMBLK_GET_ABSENT 0u    /* the iterator ended invalid, landed on another key, or the key has no
+                                   version with ts <= read_ts from the landing on */
+#define LSMBLK_GET_FOUND 1u
+#define LSMBLK_GET_TOMBSTONE 2u /* the visible version's value is empty (get_with_ts returns None,
+                                   src/lsm_storage.rs:435-438) */
+#define LSMBLK_GET_RANGE_OUT 3u /* key_within is false (src/lsm_storage.rs:136-138); no seek */
+#define LSMBLK_GET_BLOOM_OUT 4u /* Bloom::may_contain is false (src/table/bloom.rs:104-120, with its
+                                   k > 30 -> true and h % (nbits as u32)); no seek */
+
+/* flags.  Default: the reference as written -- block = max(partition_point(first_key <= key) - 1, 0)
+ * (table.rs:253-257), BlockIterator::seek_to_key's binary search that stops at the first probe
+ * comparing equal (the landing of lsmblk_seek_batch), the spill to entry 0 of the next block when
+ * the block iterator ends invalid, then LsmIterator::move_to_key (lsm_iterator.rs:59-86) over that
+ * iterator: forward while the key equals the query and ts > read_ts.  With several versions of a
+ * key the landing may lie past newer versions, which are then never seen. */
+#define LSMBLK_GET_NO_FILTER 1u /* skip key_within and the bloom test: SsTableIterator::create_and_seek_to_key alone */
+#define LSMBLK_GET_MVCC 2u      /* the corrected read: land on the first entry in SST order whose key is >=
+                                   the query (block found with first_key < key), then follow
+                                   SsTableIterator::next to the first version with ts <= read_ts */
+
+/* nq lookups: query q = (q_sst[q], qkeys[qkey_off[q] .. qkey_off[q+1]), q_ts[q]) over the opened set
+ * (files, file_off, desc, index as lsmblk_sst_open_batch left them) -> res[q].  With vals != NULL the
+ * values of the FOUND queries are gathered in query order: vals[val_off[q] .. val_off[q+1])
+ * (val_off: u32[nq+1]; not FOUND: empty); when they exceed val_cap the stats carry CAPACITY, [2]
+ * the required bytes, and vals is not written.  stats: [0] lookups  [1] FOUND  [2] value bytes
+ * [3] error flags: SEGMENTS (a q_sst >= nsst), EMPTY_KEY (an empty query key), MALFORMED (a block
+ * on a lookup's path breaks the decode rules of lsmblk_seek_batch, checked for every entry of the
+ * block); those lookups report LSMBLK_GET_ABSENT.  Every walk is bounded by the block's entry count
+ * and the SST's block count.  All device pointers (q_sst u32[nq], qkey_off u32[nq+1], q_ts
+ * u64[nq]).  Asynchronous. */
+int lsmblk_sst_get_batch(lsmblk_ctx* ctx, const uint8_t* files, const uint64_t* file_off, uint32_t nsst,
+                         const lsmblk_sst_desc* desc, const lsmblk_sst_index* index, const uint32_t* q_sst,
+                         const uint8_t* qkeys, const uint32_t* qkey_off, const uint64_t* q_ts, uint64_t nq,
+                         uint32_t flags, lsmblk_get_result* res, uint8_t* vals, uint64_t val_cap,
+                         uint32_t* val_off, uint64_t* stats, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

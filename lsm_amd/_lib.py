@@ -33,6 +33,13 @@ LSMBLK_MERGE_TWO_LEVEL = 1
 LSMBLK_TWO_END_IN_RANGE = 0
 LSMBLK_TWO_END_ABOVE = 1
 LSMBLK_TWO_END_BELOW = 2
+LSMBLK_GET_ABSENT = 0
+LSMBLK_GET_FOUND = 1
+LSMBLK_GET_TOMBSTONE = 2
+LSMBLK_GET_RANGE_OUT = 3
+LSMBLK_GET_BLOOM_OUT = 4
+LSMBLK_GET_NO_FILTER = 1
+LSMBLK_GET_MVCC = 2
 
 
 class LsmBlkError(RuntimeError):
@@ -58,6 +65,24 @@ class KernelStatC(ctypes.Structure):
 
 class KeyRangeC(ctypes.Structure):
     _fields_ = [("lo", P), ("hi", P), ("lo_len", U32), ("hi_len", U32), ("has_lo", U32), ("has_hi", U32)]
+
+
+class SstDescC(ctypes.Structure):
+    """lsmblk_sst_desc (64 bytes)."""
+    _fields_ = [("blk0", U32), ("nblk", U32), ("meta_offset", U32), ("bloom_len", U32), ("bloom_pos", U64),
+                ("first_key_pos", U64), ("last_key_pos", U64), ("first_key_len", U32), ("last_key_len", U32),
+                ("max_ts", U64), ("bloom_k", U32), ("err", U32)]
+
+
+class SstIndexC(ctypes.Structure):
+    """lsmblk_sst_index (32 bytes)."""
+    _fields_ = [("img_hi", U64), ("img_lo", U64), ("off", U32), ("end", U32), ("key_pos", U32), ("key_len", U32)]
+
+
+class GetResultC(ctypes.Structure):
+    """lsmblk_get_result (40 bytes)."""
+    _fields_ = [("status", U32), ("blk", U32), ("ent", U32), ("hit_blk", U32), ("hit_ent", U32), ("vlen", U32),
+                ("ts", U64), ("val_pos", U64)]
 
 
 # (name, restype, argtypes) for every symbol of include/lsmblk.h
@@ -130,6 +155,8 @@ SIGNATURES = [
     ("lsmblk_seek_batch", I, [P, P, P, U64, U32, P, P, P, U64, P, P, P]),
     ("lsmblk_fingerprint32", U32, [P, S]),
     ("lsmblk_bloom_may_contain", I, [P, S, U32, U32]),
+    ("lsmblk_sst_open_batch", I, [P, P, P, U32, P, P, U64, P, P]),
+    ("lsmblk_sst_get_batch", I, [P, P, P, U32, P, P, P, P, P, P, U64, U32, P, P, U64, P, P, P]),
 ]
 
 

@@ -23,107 +23,7 @@
 
 namespace {
 
-// ---------------------------------------------------------------- farmhash fingerprint32
-// farmhash 1.1.5 fingerprint32 = farmhashmk::Hash32 of Google's FarmHash (a CityHash descendant):
-// restated from the published algorithm (oracle/pyref.py has the same restatement; parity with
-// the crate itself is unpinned here -- DESIGN.md).  Rotate is a right rotation; Fetch a
-// little-endian u32 load at any byte offset.
-constexpr uint32_t kF1 = 0xcc9e2d51u, kF2 = 0x1b873593u;
-
-__host__ __device__ __forceinline__ uint32_t frot(uint32_t v, uint32_t s) { return s ? (v >> s) | (v << (32 - s)) : v; }
-__host__ __device__ __forceinline__ uint32_t ffmix(uint32_t h) {
-  h ^= h >> 16;
-  h *= 0x85ebca6bu;
-  h ^= h >> 13;
-  h *= 0xc2b2ae35u;
-  h ^= h >> 16;
-  return h;
-}
-__host__ __device__ __forceinline__ uint32_t fmur(uint32_t a, uint32_t h) {
-  a *= kF1;
-  a = frot(a, 17);
-  a *= kF2;
-  h ^= a;
-  h = frot(h, 19);
-  return h * 5 + 0xe6546b64u;
-}
-
-// Src: a byte source with u32 fetches at arbitrary offsets (bytes [i, i + 4), little-endian)
-// and single bytes.
-template <class Src>
-__host__ __device__ uint32_t fingerprint32(const Src& S, uint32_t len) {
-  if (len <= 4) {
-    uint32_t b = 0, c = 9;
-    for (uint32_t i = 0; i < len; ++i) {
-      const int32_t v = int32_t(int8_t(S.byte(i)));  // signed char
-      b = b * kF1 + uint32_t(v);
-      c ^= b;
-    }
-    return ffmix(fmur(b, fmur(len, c)));
-  }
-  if (len <= 12) {
-    uint32_t a = len, b = len * 5, c = 9, d = b;
-    a += S.fetch(0);
-    b += S.fetch(len - 4);
-    c += S.fetch((len >> 1) & 4);
-    return ffmix(fmur(c, fmur(b, fmur(a, d))));
-  }
-  if (len <= 24) {
-    uint32_t a = S.fetch((len >> 1) - 4), b = S.fetch(4), c = S.fetch(len - 8), d = S.fetch(len >> 1);
-    const uint32_t e = S.fetch(0), f = S.fetch(len - 4);
-    uint32_t h = d * kF1 + len;
-    a = frot(a, 12) + f;
-    h = fmur(c, h) + a;
-    a = frot(a, 3) + c;
-    h = fmur(e, h) + a;
-    a = frot(a + f, 12) + d;
-    h = fmur(b, h) + a;
-    return ffmix(h);
-  }
-  uint32_t h = len, g = kF1 * len, f = g;
-  const uint32_t a0 = frot(S.fetch(len - 4) * kF1, 17) * kF2, a1 = frot(S.fetch(len - 8) * kF1, 17) * kF2;
-  const uint32_t a2 = frot(S.fetch(len - 16) * kF1, 17) * kF2, a3 = frot(S.fetch(len - 12) * kF1, 17) * kF2;
-  const uint32_t a4 = frot(S.fetch(len - 20) * kF1, 17) * kF2;
-  h ^= a0;
-  h = frot(h, 19);
-  h = h * 5 + 0xe6546b64u;
-  h ^= a2;
-  h = frot(h, 19);
-  h = h * 5 + 0xe6546b64u;
-  g ^= a1;
-  g = frot(g, 19);
-  g = g * 5 + 0xe6546b64u;
-  g ^= a3;
-  g = frot(g, 19);
-  g = g * 5 + 0xe6546b64u;
-  f += a4;
-  f = frot(f, 19) + 113;
-  uint32_t iters = (len - 1) / 20, p = 0;
-  do {
-    const uint32_t a = S.fetch(p), b = S.fetch(p + 4), c = S.fetch(p + 8), d = S.fetch(p + 12), e = S.fetch(p + 16);
-    h += a;
-    g += b;
-    f += c;
-    h = fmur(d, h) + e;
-    g = fmur(c, g) + a;
-    f = fmur(b + e * kF1, f) + d;
-    f += g;
-    g += f;
-    p += 20;
-  } while (--iters != 0);
-  g = frot(g, 11) * kF1;
-  g = frot(g, 17) * kF1;
-  f = frot(f, 11) * kF1;
-  f = frot(f, 17) * kF1;
-  h = frot(h + g, 19);
-  h = h * 5 + 0xe6546b64u;
-  h = frot(h, 17) * kF1;
-  h = frot(h + f, 19);
-  h = h * 5 + 0xe6546b64u;
-  h = frot(h, 17) * kF1;
-  return h;
-}
-
+// (farmhash fingerprint32 and wave_copy_bytes live in lsmblk_dev.hpp: lsmblk_get.hip shares them)
 // A key in the KV stream's arena through a bounds-checked descriptor (aligned dword loads).
 struct DevKey {
   rsrc_t r;
@@ -245,17 +145,6 @@ __device__ __forceinline__ void put_be32(uint8_t* d, uint32_t v) {
   d[1] = uint8_t(v >> 16);
   d[2] = uint8_t(v >> 8);
   d[3] = uint8_t(v);
-}
-
-// len bytes src -> dst by the whole wave, any alignment (16-B pieces, 1 KiB per instruction).
-__device__ __forceinline__ void wave_copy_bytes(uint8_t* dst, const uint8_t* src, uint64_t len) {
-  for (uint64_t o = 16ull * lane_id(); o < len; o += 1024) {
-    if (o + 16 <= len) {
-      *reinterpret_cast<u32x4*>(dst + o) = *reinterpret_cast<const u32x4*>(src + o);
-    } else {
-      for (uint64_t x = o; x < len; ++x) dst[x] = src[x];
-    }
-  }
 }
 
 __device__ __forceinline__ uint32_t sst_of_block(const SstArgs& a, uint64_t b) {

@@ -9,6 +9,9 @@
   SsTable           SsTable::open / read_block / find_block_idx (src/table.rs:162-257) over a file
                     held in memory; blocks are decoded on the device from the framed data section
                     with the read_block CRC check (lsmblk_decode_batch_ex)
+  SstSet            SST files resident in device memory, opened once on the device
+                    (lsmblk_sst_open_batch), answering batches of (sst, key, read_ts) point lookups
+                    with the entry and its value (lsmblk_sst_get_batch)
 
 Device work goes through liblsmblk.so; the footer / section parsing here is host logic that mirrors
 the reference's own (the CRC-32 of those small sections is zlib's, which is crc32fast's).
@@ -20,7 +23,8 @@ import numpy as np
 import torch
 
 from . import batch
-from ._lib import LSMBLK_E_CAPACITY, LsmBlkError, check, lib
+from ._lib import (LSMBLK_E_CAPACITY, LSMBLK_GET_FOUND, LSMBLK_GET_MVCC, LSMBLK_GET_NO_FILTER, GetResultC, LsmBlkError,
+                   SstDescC, SstIndexC, check, lib)
 
 
 class MemTable:
@@ -211,3 +215,175 @@ class SsTable:
         data = torch.frombuffer(bytearray(self.buf[a:b]), dtype=torch.uint8).to(self.device)
         rel = torch.from_numpy((off[lo:hi + 1] - off[lo]).view(np.int64)).to(self.device)
         return batch.decode_blocks(data, rel, tail=4, verify=verify)
+
+
+ERR_CAPACITY = 2  # LSMBLK_ERR_CAPACITY
+GET_FIELDS = ("status", "blk", "ent", "hit_blk", "hit_ent", "vlen", "ts", "val_pos")
+
+
+class SstSet:
+    """SST files resident in device memory, opened once on the device (lsmblk_sst_open_batch):
+    file s = files[file_off[s]:file_off[s+1]], as sst_files returns them.  `files` is bytes, a numpy
+    u8 array or a u8 tensor; `file_off` an int64 tensor or any sequence.  A call-wide error
+    (lsmblk_sst_open_batch's stats[3]) raises LsmBlkError; an SST whose open failed keeps its flags
+    in err[s] and 0 blocks (lookups against it report ABSENT) while the others answer."""
+
+    def __init__(self, files, file_off, device="cuda", stream=None):
+        dev = torch.device(device)
+        if dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.device, self.stream = dev, stream
+        if not isinstance(files, torch.Tensor):
+            files = torch.from_numpy(np.frombuffer(bytes(files), np.uint8).copy() if isinstance(files, (bytes, bytearray))
+                                     else np.ascontiguousarray(files, np.uint8))
+        if files.device != dev or files.data_ptr() % 16 or not files.is_contiguous():
+            t = batch._aligned_empty(files.numel(), dev)
+            t[:files.numel()].copy_(files)
+            files = t
+        if not isinstance(file_off, torch.Tensor):
+            file_off = torch.from_numpy(np.ascontiguousarray(file_off, np.uint64).view(np.int64))
+        self.files, self.file_off = files, file_off.to(dev).contiguous()
+        batch._need(self.file_off, torch.int64, "file_off", dev.index, 1)
+        self.nsst = self.file_off.numel() - 1
+        self.desc_t = torch.zeros(max(self.nsst, 1) * ctypes.sizeof(SstDescC), dtype=torch.uint8, device=dev)
+        self.index_t = None
+        cap = 0
+        for _ in range(2):  # the first call sizes the block index
+            st = self._open(cap)
+            if not (st[3] & ERR_CAPACITY):
+                break
+            cap = st[1]
+            self.index_t = batch._aligned_empty(cap * ctypes.sizeof(SstIndexC), dev)
+        self.open_stats = st
+        if st[3]:
+            raise LsmBlkError(lib().lsmblk_stats_status(st[3]), "sst open")
+        self.desc = self.desc_t.cpu().numpy().view(np.dtype(SstDescC))[:self.nsst]
+        self.index = (self.index_t[:cap * ctypes.sizeof(SstIndexC)].cpu().numpy().view(np.dtype(SstIndexC))
+                      if cap else np.zeros(0, np.dtype(SstIndexC)))
+        self.err = self.desc["err"].copy()
+        self._host = None
+
+    def _open(self, index_cap):
+        stats = torch.zeros(batch.STATS_WORDS, dtype=torch.int64, device=self.device)
+        batch._native("lsmblk_sst_open_batch", self.device.index, self.stream, batch._ptr(self.files),
+                      self.file_off.data_ptr(), self.nsst, self.desc_t.data_ptr(), batch._ptr(self.index_t),
+                      index_cap, stats.data_ptr(), batch._stream_ptr(self.stream, self.device.index))
+        torch.cuda.synchronize(self.device)
+        return [int(x) & 0xFFFFFFFFFFFFFFFF for x in stats.cpu().tolist()]
+
+    # ---- what SsTable::open leaves (read back from the descriptors and the index)
+    def _file_bytes(self):
+        if self._host is None:
+            self._host = self.files.cpu().numpy()
+        return self._host
+
+    def _slice(self, pos, n):
+        return self._file_bytes()[int(pos):int(pos) + int(n)].tobytes()
+
+    def num_of_blocks(self, s):
+        return int(self.desc["nblk"][s])
+
+    def first_key(self, s):
+        return self._slice(self.desc["first_key_pos"][s], self.desc["first_key_len"][s])
+
+    def last_key(self, s):
+        return self._slice(self.desc["last_key_pos"][s], self.desc["last_key_len"][s])
+
+    def max_ts(self, s):
+        return int(self.desc["max_ts"][s])
+
+    def bloom_k(self, s):
+        return int(self.desc["bloom_k"][s])
+
+    def bloom_filter(self, s):
+        return self._slice(self.desc["bloom_pos"][s], self.desc["bloom_len"][s])
+
+    def _records(self, s):
+        b0 = int(self.desc["blk0"][s])
+        return self.index[b0:b0 + int(self.desc["nblk"][s])]
+
+    def block_offsets(self, s):
+        """Framed block ranges of SST s: BlockMeta offsets, then the meta section (as SsTable.block_offsets)."""
+        r = self._records(s)
+        return np.array(list(r["off"]) + [int(self.desc["meta_offset"][s])] if len(r) else [], np.uint64)
+
+    def block_meta(self, s):
+        """[(offset, end, first_key)] per block of SST s."""
+        fo = int(self.file_off[s].item())
+        return [(int(r["off"]), int(r["end"]), self._slice(fo + int(r["key_pos"]), r["key_len"])) for r in self._records(s)]
+
+    # ---- lookups
+    def get_into(self, q_sst, qkeys, qkey_off, q_ts, nq, flags, res, stats, vals=None, val_cap=0, val_off=None):
+        """Asynchronous lsmblk_sst_get_batch over device tensors (no host sync): q_sst / qkey_off int32
+        (u32), q_ts int64 (u64), res uint8[40 nq], stats int64[4]; vals / val_off None: no gather."""
+        dev = self.device.index
+        batch._need(q_sst, torch.int32, "q_sst", dev, nq)
+        batch._need(qkey_off, torch.int32, "qkey_off", dev, nq + 1)
+        batch._need(q_ts, torch.int64, "q_ts", dev, nq)
+        batch._need(res, torch.uint8, "res", dev, nq * ctypes.sizeof(GetResultC))
+        batch._need(stats, torch.int64, "stats", dev, batch.STATS_WORDS)
+        if vals is not None:
+            batch._need(vals, torch.uint8, "vals", dev, val_cap)
+            batch._need(val_off, torch.int32, "val_off", dev, nq + 1)
+        batch._native("lsmblk_sst_get_batch", dev, self.stream, batch._ptr(self.files), self.file_off.data_ptr(),
+                      self.nsst, self.desc_t.data_ptr(), batch._ptr(self.index_t), q_sst.data_ptr(), qkeys.data_ptr(),
+                      qkey_off.data_ptr(), q_ts.data_ptr(), nq, flags, res.data_ptr(),
+                      vals.data_ptr() if vals is not None else None, val_cap if vals is not None else 0,
+                      val_off.data_ptr() if vals is not None else None, stats.data_ptr(),
+                      batch._stream_ptr(self.stream, dev))
+
+    def upload_queries(self, q_sst, keys, read_ts):
+        """Host queries -> the device tensors of get_into: (q_sst, qkeys, qkey_off, q_ts)."""
+        dev, nq = self.device, len(keys)
+        kb = b"".join(bytes(k) for k in keys)
+        ko = np.zeros(nq + 1, np.uint32)
+        if nq:
+            ko[1:] = np.cumsum([len(k) for k in keys])
+        qk = batch._aligned_empty(len(kb) + 16, dev)
+        if kb:
+            qk[:len(kb)].copy_(torch.frombuffer(bytearray(kb), dtype=torch.uint8))
+        qs = batch._u32_table(np.ascontiguousarray(q_sst, np.uint32).reshape(-1) if nq else np.zeros(1, np.uint32), dev)
+        ts = np.broadcast_to(np.asarray(read_ts, np.uint64), (nq,)).copy() if nq else np.zeros(1, np.uint64)
+        qt = torch.from_numpy(ts.view(np.int64)).to(dev)
+        return qs, qk, batch._u32_table(ko, dev), qt
+
+    def get_raw(self, q_sst, keys, read_ts, flags=0, val_cap=None, vals=None):
+        """One lsmblk_sst_get_batch call -> (results as a numpy record array, vals tensor or None,
+        val_off numpy or None, stats list); nothing raises on the stats.  val_cap None: no gather."""
+        dev, nq = self.device, len(keys)
+        qs, qk, qo, qt = self.upload_queries(q_sst, keys, read_ts)
+        res = torch.zeros(max(nq, 1) * ctypes.sizeof(GetResultC), dtype=torch.uint8, device=dev)
+        stats = torch.zeros(batch.STATS_WORDS, dtype=torch.int64, device=dev)
+        vo = None
+        if val_cap is not None:
+            if vals is None:
+                vals = batch._aligned_empty(val_cap, dev)
+            vo = torch.zeros(nq + 1, dtype=torch.int32, device=dev)
+        self.get_into(qs, qk, qo, qt, nq, flags, res, stats, vals if val_cap is not None else None, val_cap or 0, vo)
+        torch.cuda.synchronize(dev)
+        r = res.cpu().numpy().view(np.dtype(GetResultC))[:nq]
+        st = [int(x) & 0xFFFFFFFFFFFFFFFF for x in stats.cpu().tolist()]
+        return r, vals, (vo.cpu().numpy().view(np.uint32) if vo is not None else None), st
+
+    def get(self, q_sst, keys, read_ts, *, no_filter=False, mvcc=False, values=True):
+        """Batched point lookups: query i = (q_sst[i], keys[i], read_ts[i] or the scalar read_ts) ->
+        dict of numpy arrays (status, blk, ent, hit_blk, hit_ent, vlen, ts, val_pos; LSMBLK_GET_*
+        statuses) and, with `values`, "values": a list of the FOUND lookups' value bytes (None for
+        the others) and "val_off"."""
+        flags = (LSMBLK_GET_NO_FILTER if no_filter else 0) | (LSMBLK_GET_MVCC if mvcc else 0)
+        cap = 64 * len(keys) + 1024 if values else None
+        for _ in range(2):
+            r, vals, vo, st = self.get_raw(q_sst, keys, read_ts, flags, cap)
+            if values and st[3] == ERR_CAPACITY:
+                cap = st[2]
+                continue
+            break
+        if st[3]:
+            raise LsmBlkError(lib().lsmblk_stats_status(st[3]), "sst get")
+        out = {f: r[f].copy() for f in GET_FIELDS}
+        if values:
+            hv = vals[:int(vo[-1])].cpu().numpy() if len(vo) else np.zeros(0, np.uint8)
+            out["val_off"] = vo
+            out["values"] = [hv[vo[i]:vo[i + 1]].tobytes() if r["status"][i] == LSMBLK_GET_FOUND else None
+                             for i in range(len(keys))]
+        return out
