@@ -181,6 +181,9 @@ int lsmblk_ctx_reserve(lsmblk_ctx* ctx, uint64_t max_blocks, uint64_t max_entrie
                                        every fifth block's first entry is set past its end entry (a
                                        block table with e < s, and e > n at the end); emit must report
                                        LSMBLK_E_INTERNAL and read none of those entries */
+#define LSMBLK_DEBUG_SCAN_UNITS 11 /* work units (waves' worth of blocks) lsmblk_sst_scan_batch spreads a batch's
+                                      blocks over beyond one per range (default 131072; 0 restores it): with
+                                      more blocks than units a unit takes several consecutive blocks */
 int lsmblk_debug_set(lsmblk_ctx* ctx, int key, uint32_t value);
 /* The trace of the last lagged decode with LSMBLK_DEBUG_COUNTERS on (n <= 16 + 8 * 32768 words;
  * synchronizes).  Words 16 + 8 t + k, 100 MHz s_memrealtime stamps of 64-block tile t: k = 0 tile
@@ -637,6 +640,85 @@ int lsmblk_sst_get_batch(lsmblk_ctx* ctx, const uint8_t* files, const uint64_t* 
                          const uint8_t* qkeys, const uint32_t* qkey_off, const uint64_t* q_ts, uint64_t nq,
                          uint32_t flags, lsmblk_get_result* res, uint8_t* vals, uint64_t val_cap,
                          uint32_t* val_off, uint64_t* stats, void* stream);
+
+/* ------------------------------------------------------------------ SST range scans (device) */
+/* The read side's range read (scan_with_ts, src/lsm_storage.rs:446-550) over the opened set of the
+ * point lookups: per SST the raw range scan (lsmblk_sst_scan_batch), across SSTs lsmblk_merge_batch
+ * with the scans' seg_start as run_start, then the reader's view at read_ts
+ * (lsmblk_read_filter_batch). */
+
+/* Bound kinds of q_bound: bits 0-1 the lower bound, bits 2-3 the upper bound (std::ops::Bound). */
+#define LSMBLK_BOUND_UNBOUNDED 0u
+#define LSMBLK_BOUND_INCLUDED 1u
+#define LSMBLK_BOUND_EXCLUDED 2u
+
+/* Result of one range (32 bytes).  Positions are SST-local (block, entry); blk == nblk with ent 0 is
+ * the SST's end; all four are 0xFFFFFFFF when no seek was made (RANGE_OUT, a failed open, a bad
+ * query) or a block on the range's path is malformed. */
+typedef struct {
+  uint32_t status;     /* LSMBLK_SCAN_* */
+  uint32_t blk0, ent0; /* begin */
+  uint32_t blk1, ent1; /* end, exclusive */
+  uint32_t blocks;     /* blocks holding an entry of [begin, end) */
+  uint64_t n;          /* entries of [begin, end) */
+} lsmblk_scan_result;
+
+#define LSMBLK_SCAN_OK 0u        /* n > 0 */
+#define LSMBLK_SCAN_EMPTY 1u     /* the range holds no entry */
+#define LSMBLK_SCAN_RANGE_OUT 2u /* range_overlap is false (src/lsm_storage.rs:142-167); no seek */
+
+/* flags (the values of LSMBLK_GET_NO_FILTER / LSMBLK_GET_MVCC) */
+#define LSMBLK_SCAN_NO_FILTER 1u /* skip range_overlap */
+#define LSMBLK_SCAN_MVCC 2u      /* an Included / Excluded lower bound lands on the first entry in SST order
+                                    with key >= the bound instead of the reference's landing */
+
+/* nq raw range scans, the SsTableIterator that scan_with_ts builds per table
+ * (src/lsm_storage.rs:474-502) run to its end bound: query q = SST q_sst[q], lower key
+ * lkeys[lkey_off[q] .. lkey_off[q+1]), upper key ukeys[ukey_off[q] .. ukey_off[q+1]), kinds q_bound[q]
+ * (an unbounded side's key is ignored; an empty key with a bounded kind raises EMPTY_KEY and the
+ * range is empty).
+ *   range_overlap against the SST's first / last key fails: LSMBLK_SCAN_RANGE_OUT.
+ *   begin: Unbounded (0, 0); Included(k) the landing of SsTableIterator::create_and_seek_to_key(k),
+ *     the (blk, ent) of lsmblk_sst_get_batch with LSMBLK_GET_NO_FILTER in the same mode; Excluded(k)
+ *     that landing, then forward while the entry's key equals k (:487-496), across block ends.
+ *   end: the first entry at or after begin with key > upper (Included) or >= upper (Excluded); the
+ *     SST's end for an unbounded upper.  The bound is tested on every entry, the landing included:
+ *     LsmIterator::new does not test its first position (src/lsm_iterator.rs:29-43), a quirk of the
+ *     merged iterator that is deliberately not reproduced per SST.
+ *   The end comes from the index search and one in-block count (SST entries are in key order; for
+ *   files that are not the result is unspecified, every walk bounded by entry and block counts).
+ * res[q]: the positions and the entry count.  out (may be NULL: sizes only) receives every version
+ * of every entry of [begin, end), range after range in query order, with the bytes
+ * lsmblk_decode_batch_ex gives for them (any alignment); seg_start (u32[nq+1], required) = each
+ * range's first entry in out, the run_start shape of lsmblk_merge_batch.  Overlapping and repeated
+ * ranges are each written in full.
+ * stats: [0] entries [1] key bytes [2] value bytes [3] error flags: CAPACITY (a capacity of out is
+ * too small: [0..2] hold the required sizes, nothing is written to out; res and seg_start are),
+ * OVERFLOW (a total does not fit u32), SEGMENTS (a q_sst >= nsst or a bound kind of 3), EMPTY_KEY,
+ * MALFORMED (a visited block breaks the decode rules, every entry of every visited block being
+ * checked: that range is empty, LSMBLK_SCAN_EMPTY).  A query on an SST whose open failed is EMPTY.
+ * All device pointers.  Asynchronous; workspace on the context (32 B per query + 3 MiB). */
+int lsmblk_sst_scan_batch(lsmblk_ctx* ctx, const uint8_t* files, const uint64_t* file_off, uint32_t nsst,
+                          const lsmblk_sst_desc* desc, const lsmblk_sst_index* index, const uint32_t* q_sst,
+                          const uint8_t* lkeys, const uint32_t* lkey_off, const uint8_t* ukeys,
+                          const uint32_t* ukey_off, const uint32_t* q_bound, uint64_t nq, uint32_t flags,
+                          lsmblk_scan_result* res, const lsmblk_kv_stream* out, uint32_t* seg_start,
+                          uint64_t* stats, void* stream);
+
+/* What a reader at read_ts sees of each segment of `in` (segment s = entries [seg_start[s],
+ * seg_start[s+1]), seg_start u32[nseg+1] non-decreasing with seg_start[nseg] <= in->n; read_ts =
+ * seg_ts[s], u64[nseg]): LsmIterator::move_to_key / next (src/lsm_iterator.rs:45-86) over an inner
+ * iterator yielding the segment.  Within a segment user keys must ascend with versions newest
+ * first (a raw scan of a builder-written SST, which may begin in the middle of a key's versions,
+ * or lsmblk_merge_batch's output); then entry i is kept iff ts[i] <= read_ts, its value is not
+ * empty, and i is the segment's first entry or key[i-1] != key[i] or ts[i-1] > read_ts.  Nothing
+ * is compared across a segment boundary; entries outside every segment are dropped.  The kept
+ * entries go in order to `out` (any alignment); out_seg_start (u32[nseg+1]) = each segment's kept
+ * range.  stats: [0] kept entries [1] key bytes [2] value bytes [3] error flags (CAPACITY: the
+ * required sizes, nothing written to out's arenas; SEGMENTS: a bad seg_start).  Asynchronous. */
+int lsmblk_read_filter_batch(lsmblk_ctx* ctx, const lsmblk_kv_stream* in, const uint32_t* seg_start,
+                             const uint64_t* seg_ts, uint32_t nseg, const lsmblk_kv_stream* out,
+                             uint32_t* out_seg_start, uint64_t* stats, void* stream);
 
 #ifdef __cplusplus
 }

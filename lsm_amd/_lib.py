@@ -40,6 +40,15 @@ LSMBLK_GET_RANGE_OUT = 3
 LSMBLK_GET_BLOOM_OUT = 4
 LSMBLK_GET_NO_FILTER = 1
 LSMBLK_GET_MVCC = 2
+LSMBLK_BOUND_UNBOUNDED = 0
+LSMBLK_BOUND_INCLUDED = 1
+LSMBLK_BOUND_EXCLUDED = 2
+LSMBLK_SCAN_OK = 0
+LSMBLK_SCAN_EMPTY = 1
+LSMBLK_SCAN_RANGE_OUT = 2
+LSMBLK_SCAN_NO_FILTER = 1
+LSMBLK_SCAN_MVCC = 2
+LSMBLK_DEBUG_SCAN_UNITS = 11
 
 
 class LsmBlkError(RuntimeError):
@@ -83,6 +92,12 @@ class GetResultC(ctypes.Structure):
     """lsmblk_get_result (40 bytes)."""
     _fields_ = [("status", U32), ("blk", U32), ("ent", U32), ("hit_blk", U32), ("hit_ent", U32), ("vlen", U32),
                 ("ts", U64), ("val_pos", U64)]
+
+
+class ScanResultC(ctypes.Structure):
+    """lsmblk_scan_result (32 bytes)."""
+    _fields_ = [("status", U32), ("blk0", U32), ("ent0", U32), ("blk1", U32), ("ent1", U32), ("blocks", U32),
+                ("n", U64)]
 
 
 # (name, restype, argtypes) for every symbol of include/lsmblk.h
@@ -157,6 +172,9 @@ SIGNATURES = [
     ("lsmblk_bloom_may_contain", I, [P, S, U32, U32]),
     ("lsmblk_sst_open_batch", I, [P, P, P, U32, P, P, U64, P, P]),
     ("lsmblk_sst_get_batch", I, [P, P, P, U32, P, P, P, P, P, P, U64, U32, P, P, U64, P, P, P]),
+    ("lsmblk_sst_scan_batch", I, [P, P, P, U32, P, P, P, P, P, P, P, P, U64, U32, P, ctypes.POINTER(KVStreamC), P, P,
+                                  P]),
+    ("lsmblk_read_filter_batch", I, [P, ctypes.POINTER(KVStreamC), P, P, U32, ctypes.POINTER(KVStreamC), P, P, P]),
 ]
 
 

@@ -547,6 +547,47 @@ def compact_filter(kv: KVStream, watermark: int, bottom_level: bool, prefixes=()
     return out
 
 
+def read_filter_into(kv: KVStream, seg_start: torch.Tensor, seg_ts: torch.Tensor, nseg: int, out: KVStream,
+                     out_seg_start: torch.Tensor, stats, stream=None, caps=None):
+    """Asynchronous lsmblk_read_filter_batch into preallocated `out` (no host sync): seg_start /
+    out_seg_start int32 (u32) [nseg + 1], seg_ts int64 (u64) [nseg]."""
+    dev = _dev_index(seg_start)
+    kv.check(dev, "kv")
+    _need(seg_start, torch.int32, "seg_start", dev, nseg + 1)
+    _need(seg_ts, torch.int64, "seg_ts", dev, nseg)
+    _need(out_seg_start, torch.int32, "out_seg_start", dev, nseg + 1)
+    out.check(dev, "out", 0)
+    _need(stats, torch.int64, "stats", dev, STATS_WORDS)
+    ci, co = kv._c(), out._c(*(caps if caps is not None else out.caps()))
+    _native("lsmblk_read_filter_batch", dev, stream, ctypes.byref(ci), seg_start.data_ptr(), seg_ts.data_ptr(), nseg,
+            ctypes.byref(co), out_seg_start.data_ptr(), stats.data_ptr(), _stream_ptr(stream, dev),
+            what="lsmblk_read_filter_batch")
+
+
+def read_filter(kv: KVStream, seg_start, read_ts, stream=None):
+    """What a reader sees of every segment kv[seg_start[s]:seg_start[s+1]] at read_ts (one for all
+    segments, or one per segment): LsmIterator (reference src/lsm_iterator.rs:45-86) over each
+    segment -- per key its newest version at or below read_ts, unless that is a tombstone.  Within
+    a segment keys ascend, versions newest first (a raw SST scan, merge_runs' output).
+    -> (the kept entries as a new KVStream, their seg_start as a numpy u32 array)."""
+    dev = torch.device("cuda", _dev_index(kv.key_off))
+    ss = _u32_table(seg_start, dev)
+    nseg = ss.numel() - 1
+    ts = np.broadcast_to(np.asarray(read_ts, np.uint64), (nseg,)).copy() if nseg else np.zeros(1, np.uint64)
+    st_t = torch.from_numpy(ts.view(np.int64)).to(dev)
+    kb, vb = kv.byte_sizes()
+    out = KVStream.empty(kv.n, kb, vb, dev)
+    oss = torch.zeros(nseg + 1, dtype=torch.int32, device=dev)
+    stats = torch.zeros(STATS_WORDS, dtype=torch.int64, device=dev)
+    read_filter_into(kv, ss, st_t, nseg, out, oss, stats, stream)
+    torch.cuda.synchronize(dev)
+    st = _status(stats)
+    if st:
+        raise LsmBlkError(st, "read_filter")
+    out.n = int(stats[0].item())
+    return out, oss.cpu().numpy().view(np.uint32)
+
+
 def merge_into(kv: KVStream, run_start: torch.Tensor, nrun: int, out: KVStream, stats, stream=None,
                merge_mode=LSMBLK_MERGE_RUNS):
     """Asynchronous merge of the runs of kv into preallocated `out` (no host sync): MergeIterator

@@ -699,6 +699,7 @@ inline void crc_stream_host_tables(CrcStreamTabs& T) {
 
 constexpr uint32_t kDecLagDefault = 10240;
 constexpr uint64_t kDecLagBytesDefault = 10240ull * 4096;
+constexpr uint32_t kScanUnitsDefault = 1u << 17;
 
 struct lsmblk_ctx {
   int device = 0;
@@ -782,6 +783,9 @@ struct lsmblk_ctx {
   // SST files (lsmblk_sst.hip)
   uint8_t* sws = nullptr;
   uint64_t sws_cap = 0;
+  // range scans (lsmblk_sst_scan_batch): the work units a batch's blocks are spread over beyond
+  // one per range (LSMBLK_DEBUG_SCAN_UNITS); the workspace is carved from sws
+  uint32_t scan_units = kScanUnitsDefault;
   // key-range shard rotation (lsmblk_shard_*): its own arena, carved from the parameters of the
   // last lsmblk_shard_rotation_prepare, which the carry and encode calls replay
   uint8_t* rws = nullptr;

@@ -17,6 +17,11 @@
 //                           the version walk
 //     val_scan_kernel       value sizes of the FOUND lookups -> val_off (one workgroup)
 //     val_gather_kernel     one wave per FOUND lookup copies its value
+//   lsmblk_sst_scan_batch   raw range scans of one SST per query (scan_with_ts's SsTableIterator per
+//                           table, lsm_storage.rs:474-502, run to its end bound); the end bound is
+//                           tested on every entry, the landing included -- LsmIterator::new's untested
+//                           first position (lsm_iterator.rs:29-43) belongs to the merged iterator and
+//                           is not reproduced per SST.  Kernels: see "scan" below
 #include "lsmblk_dev.hpp"
 
 namespace {
@@ -346,6 +351,42 @@ __device__ __forceinline__ uint32_t kary_first_false(uint32_t lo, uint32_t hi, P
   return uni(lo + uint32_t(__builtin_popcountll(__ballot(p))));
 }
 
+// partition_point of an SST's block first keys against the query: the blocks with first_key <= q
+// (strict: < q), by the k-ary search over the first-key images; blocks whose image equals the
+// query's, [iL, iU), compare whole keys.
+__device__ __forceinline__ uint32_t index_partition(const lsmblk_sst_index* ix, const uint8_t* F, uint32_t nblk,
+                                                    const QKey& q, bool strict) {
+  uint64_t qhi, qlo;
+  {
+    uint32_t w[4];
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j) {
+      const uint32_t nv = q.len > 4 * j ? q.len - 4 * j : 0u;
+      const uint32_t v = __builtin_bswap32(q.fetch(4 * j));
+      w[j] = nv >= 4 ? v : (nv ? v & ~(~0u >> (8 * nv)) : 0u);
+    }
+    qhi = (uint64_t(w[0]) << 32) | w[1];
+    qlo = (uint64_t(w[2]) << 32) | w[3];
+  }
+  const uint32_t iL = kary_first_false(0, nblk, [&](uint32_t i) {
+    const u32x4 v = *reinterpret_cast<const u32x4*>(ix + i);
+    const uint64_t hi = (uint64_t(v.y) << 32) | v.x, lo = (uint64_t(v.w) << 32) | v.z;
+    return hi < qhi || (hi == qhi && lo < qlo);
+  });
+  const uint32_t iU = kary_first_false(iL, nblk, [&](uint32_t i) {
+    const u32x4 v = *reinterpret_cast<const u32x4*>(ix + i);
+    const uint64_t hi = (uint64_t(v.y) << 32) | v.x, lo = (uint64_t(v.w) << 32) | v.z;
+    return hi < qhi || (hi == qhi && lo <= qlo);
+  });
+  uint32_t P = iL;
+  if (iU > iL)
+    P = kary_first_false(iL, iU, [&](uint32_t i) {
+      const int c = lane_cmp(F + ix[i].key_pos, ix[i].key_len, q);
+      return strict ? c < 0 : c <= 0;
+    });
+  return P;
+}
+
 struct BlkHdr {
   uint32_t n, data_end, fks;
   bool ok;
@@ -367,31 +408,12 @@ __device__ __forceinline__ BlkHdr get_hdr(const Img& im, uint32_t len) {
   return h;
 }
 
-// What one visited block decides.
-struct Visit {
-  bool done;      // the lookup is answered (else: go on with the next block)
-  bool bad;       // the block breaks the decode rules
-};
-
-struct Look {     // a lookup's state across the blocks it visits (wave-uniform)
-  uint32_t status, blk, ent, hit_blk, hit_ent, vlen;
-  uint64_t ts, val_pos;
-  bool landed;
-};
-
-// Block b of the SST (len bytes at absolute position bpos, read through im): `first` = the block the
-// block search chose, else a block the iterator moved on to (its entry 0 is the next entry).
-//   every lane compares its own entries with the query: L = entries below it, U = entries not above
-//   it, so [L, U) is the equal range (the block is sorted);
-//   first block: the landing is L (MVCC) or what the reference's binary search reaches, replayed
-//   on L / U without touching memory (mid < L: less, mid >= U: greater, else equal and it stops);
-//   then the first version of [landing, U) with ts <= read_ts.
+// The block's entries against the query, every lane comparing its own: L = entries below it, U =
+// entries not above it, so [L, U) is the equal range (the block is sorted).  Every entry is parsed
+// and checked; false: the block breaks the decode rules.
 template <class Img>
-__device__ Visit visit_block(const Img& im, uint32_t len, uint64_t bpos, uint32_t b, bool first, bool mvcc,
-                             const QKey& q, uint64_t read_ts, Look& k) {
+__device__ __forceinline__ bool block_lu(const Img& im, const BlkHdr& h, const QKey& q, uint32_t& L, uint32_t& U) {
   const uint32_t l = lane_id();
-  const BlkHdr h = get_hdr(im, len);
-  if (!h.ok) return Visit{true, true};
   // m = lcp(first key, query); an entry that shares more than m bytes with the first key orders
   // against the query as the first key does at byte m, one that shares at most m has its first
   // `prefix` bytes equal to the query's and is decided by its suffix
@@ -399,7 +421,8 @@ __device__ Visit visit_block(const Img& im, uint32_t len, uint64_t bpos, uint32_
   int cfk = 0;
   if (h.n) cfk = wave_cmp([&](uint32_t i) { return im.u8(4 + i); }, h.fks, q, m);
   const int cbeyond = m == q.len ? 1 : cfk;
-  uint32_t L = 0, U = 0;
+  L = 0;
+  U = 0;
   bool bad = false;
   for (uint32_t c = 0; c < h.n; c += 64) {
     const uint32_t e = c + l;
@@ -428,9 +451,39 @@ __device__ Visit visit_block(const Img& im, uint32_t len, uint64_t bpos, uint32_
     L += uint32_t(__builtin_popcountll(__ballot(e < h.n && cm < 0)));
     U += uint32_t(__builtin_popcountll(__ballot(e < h.n && cm <= 0)));
   }
-  if (__ballot(bad)) return Visit{true, true};
+  if (__ballot(bad)) return false;
   L = uni(L);
   U = uni(U);
+  return true;
+}
+
+// What one visited block decides.
+struct Visit {
+  bool done;      // the lookup is answered (else: go on with the next block)
+  bool bad;       // the block breaks the decode rules
+};
+
+struct Look {     // a lookup's state across the blocks it visits (wave-uniform)
+  uint32_t status, blk, ent, hit_blk, hit_ent, vlen;
+  uint64_t ts, val_pos;
+  bool landed;
+};
+
+// Block b of the SST (len bytes at absolute position bpos, read through im): `first` = the block the
+// block search chose, else a block the iterator moved on to (its entry 0 is the next entry).
+//   every lane compares its own entries with the query: L = entries below it, U = entries not above
+//   it, so [L, U) is the equal range (the block is sorted);
+//   first block: the landing is L (MVCC) or what the reference's binary search reaches, replayed
+//   on L / U without touching memory (mid < L: less, mid >= U: greater, else equal and it stops);
+//   then the first version of [landing, U) with ts <= read_ts.
+template <class Img>
+__device__ Visit visit_block(const Img& im, uint32_t len, uint64_t bpos, uint32_t b, bool first, bool mvcc,
+                             const QKey& q, uint64_t read_ts, Look& k) {
+  const uint32_t l = lane_id();
+  const BlkHdr h = get_hdr(im, len);
+  if (!h.ok) return Visit{true, true};
+  uint32_t L = 0, U = 0;
+  if (!block_lu(im, h, q, L, U)) return Visit{true, true};
   uint32_t from = 0;  // the walk starts here
   if (first) {
     uint32_t land = L;
@@ -558,37 +611,9 @@ __global__ __launch_bounds__(64 * kGetWaves) __attribute__((amdgpu_waves_per_eu(
           }
         }
       }
-      // find_block_idx (table.rs:253-257): P = partition_point(first_key <= key) (MVCC: < key) over
-      // the first-key images; blocks whose image equals the query's, [iL, iU), compare whole keys
-      uint64_t qhi, qlo;
-      {
-        uint32_t w[4];
-#pragma unroll
-        for (uint32_t j = 0; j < 4; ++j) {
-          const uint32_t nv = q.len > 4 * j ? q.len - 4 * j : 0u;
-          const uint32_t v = __builtin_bswap32(q.fetch(4 * j));
-          w[j] = nv >= 4 ? v : (nv ? v & ~(~0u >> (8 * nv)) : 0u);
-        }
-        qhi = (uint64_t(w[0]) << 32) | w[1];
-        qlo = (uint64_t(w[2]) << 32) | w[3];
-      }
+      // find_block_idx (table.rs:253-257): P = partition_point(first_key <= key) (MVCC: < key)
       const lsmblk_sst_index* const ix = a.index + blk0;
-      const uint32_t iL = kary_first_false(0, nblk, [&](uint32_t i) {
-        const u32x4 v = *reinterpret_cast<const u32x4*>(ix + i);
-        const uint64_t hi = (uint64_t(v.y) << 32) | v.x, lo = (uint64_t(v.w) << 32) | v.z;
-        return hi < qhi || (hi == qhi && lo < qlo);
-      });
-      const uint32_t iU = kary_first_false(iL, nblk, [&](uint32_t i) {
-        const u32x4 v = *reinterpret_cast<const u32x4*>(ix + i);
-        const uint64_t hi = (uint64_t(v.y) << 32) | v.x, lo = (uint64_t(v.w) << 32) | v.z;
-        return hi < qhi || (hi == qhi && lo <= qlo);
-      });
-      uint32_t P = iL;
-      if (iU > iL)
-        P = kary_first_false(iL, iU, [&](uint32_t i) {
-          const int c = lane_cmp(F + ix[i].key_pos, ix[i].key_len, q);
-          return mvcc ? c < 0 : c <= 0;
-        });
+      const uint32_t P = index_partition(ix, F, nblk, q, mvcc);
       uint32_t b = P ? P - 1 : 0;
       bool first = true;
       for (;;) {
@@ -701,6 +726,524 @@ __global__ __launch_bounds__(256) void val_gather_kernel(GetArgs a) {
   }
 }
 
+// ---------------------------------------------------------------- scan
+// lsmblk_sst_scan_batch: five launches, no device-side waits.
+//   scan_bounds_kernel   one wave per range: range_overlap, begin (the point read's landing, the
+//                        Excluded skip), end (a second index search and one in-block count) ->
+//                        positions and the blocks the range touches
+//   scan_units_kernel    one workgroup: blocks per unit = ceil(touched blocks / unit budget), units
+//                        per range, their exclusive scan.  A unit is (range, up to `bpu` consecutive
+//                        blocks), so a batch has at most nq + budget units whatever it touches and
+//                        the workspace is sized without reading anything back
+//   scan_count_kernel    one wave per unit: its blocks parsed and checked, clipped to the range's
+//                        entry window -> entries, key bytes, value bytes
+//   scan_offsets_kernel  one workgroup: the three-component scan over units (a malformed range's
+//                        units count nothing), totals, capacity / overflow, sentinels, seg_start,
+//                        res[q].n and the final statuses
+//   scan_emit_kernel     one wave per unit: offsets and ts by the entry lanes, key prefix, key suffix
+//                        and value of four entries at a time copied in 16-B pieces by 16 lanes each
+constexpr uint32_t kScanWg = 1024;  // threads of the two one-workgroup scans: each takes a contiguous share
+
+struct ScanArgs {
+  const uint8_t* files;
+  const uint64_t* file_off;
+  uint32_t nsst;
+  const lsmblk_sst_desc* desc;
+  const lsmblk_sst_index* index;
+  const uint32_t* q_sst;
+  const uint8_t* lkeys;
+  const uint32_t* lkey_off;
+  const uint8_t* ukeys;
+  const uint32_t* ukey_off;
+  const uint32_t* q_bound;
+  uint64_t nq;
+  uint32_t flags;
+  lsmblk_scan_result* res;
+  uint8_t* okeys;
+  uint32_t* okey_off;
+  uint8_t* ovals;
+  uint32_t* oval_off;
+  uint64_t* ots;
+  uint64_t entry_cap, key_cap, val_cap;
+  uint32_t has_out;
+  uint32_t* seg_start;
+  uint32_t* ubase;   // nq + 1: first unit of every range
+  uint32_t* qbad;    // nq: a block of the range is malformed
+  uint64_t* hdr;     // [0] units, [1] blocks per unit
+  uint64_t* ucnt;    // 3 per unit: counts, then their exclusive prefixes
+  uint32_t budget;
+  uint64_t* stats;
+};
+
+// Block b of the SST through its LDS image S (up to kGetLdsBlock bytes) or a bounds-checked
+// descriptor: fn(image, block bytes) -> its verdict; false when the index record's range is not a
+// framed block inside the data section.
+template <class Fn>
+__device__ __forceinline__ bool on_block(const uint8_t* F, const lsmblk_sst_index* ix, uint32_t b, uint32_t meta_offset,
+                                         uint8_t* S, Fn fn) {
+  const uint32_t l = lane_id();
+  const uint32_t off = uni(ix[b].off), end = uni(ix[b].end);
+  if (!(end >= off + 4 + 2 && end <= meta_offset)) return false;
+  const uint32_t len = end - off - 4;
+  const uint8_t* src = F + off;
+  const uint32_t lead = uni(uint32_t(reinterpret_cast<uintptr_t>(src) & 15));
+  if (len <= kGetLdsBlock) {
+    const uint32_t nch = (lead + len + 15) >> 4;  // inside the file: see sst_get_kernel
+    u32x4 p[(kGetLdsBlock + 15 + 15) / 1024 + 1];
+    wave_sync();
+#pragma unroll
+    for (uint32_t i = 0; i < sizeof(p) / sizeof(p[0]); ++i)
+      if (l + 64 * i < nch) p[i] = *reinterpret_cast<const u32x4*>(src - lead + 16 * (l + 64 * i));
+#pragma unroll
+    for (uint32_t i = 0; i < sizeof(p) / sizeof(p[0]); ++i)
+      if (l + 64 * i < nch) *reinterpret_cast<u32x4*>(S + 16 * (l + 64 * i)) = p[i];
+    wave_sync();
+    return fn(LdsImg{S, lead}, len);
+  }
+  const rsrc_t R = make_rsrc(reinterpret_cast<const uint8_t*>(uni64(reinterpret_cast<uintptr_t>(src - lead))),
+                             uni(lead + len));
+  return fn(GlbImg{R, lead}, len);
+}
+
+// Entry e of a block by the decode's rules -> its offset, prefix, suffix and value lengths.
+template <class Img>
+__device__ __forceinline__ bool parse_entry(const Img& im, const BlkHdr& h, uint32_t e, uint32_t& off, uint32_t& pf,
+                                            uint32_t& sf, uint32_t& vl) {
+  off = im.u16(h.data_end + 2 * e);
+  if (off + 4 > h.data_end) return false;
+  pf = im.u16(off);
+  sf = im.u16(off + 2);
+  if (!(off + 4 + sf + 10 <= h.data_end && pf <= h.fks && pf + sf > 0)) return false;
+  vl = im.u16(off + 12 + sf);
+  return off + 14 + sf + vl <= h.data_end;
+}
+
+// (entries below the key, entries not above it, entries) of block b; false: malformed
+__device__ __forceinline__ bool scan_lu(const uint8_t* F, const lsmblk_sst_index* ix, uint32_t b, uint32_t meta_offset,
+                                        uint8_t* S, const QKey& q, uint32_t& L, uint32_t& U, uint32_t& n) {
+  return on_block(F, ix, b, meta_offset, S, [&](const auto& im, uint32_t len) {
+    const BlkHdr h = get_hdr(im, len);
+    if (!h.ok) return false;
+    n = h.n;
+    return block_lu(im, h, q, L, U);
+  });
+}
+
+__global__ __launch_bounds__(64 * kGetWaves) void scan_bounds_kernel(ScanArgs a) {
+  __shared__ __attribute__((aligned(16))) uint8_t img[kGetWaves][kGetImg];
+  const uint32_t l = lane_id();
+  uint8_t* const S = img[wave_id()];
+  const bool mvcc = (a.flags & LSMBLK_SCAN_MVCC) != 0, filter = !(a.flags & LSMBLK_SCAN_NO_FILTER);
+  const uint32_t llead = uint32_t(reinterpret_cast<uintptr_t>(a.lkeys) & 3);
+  const uint32_t ulead = uint32_t(reinterpret_cast<uintptr_t>(a.ukeys) & 3);
+  uint32_t err = 0;
+  const uint64_t stride = uint64_t(gridDim.x) * kGetWaves;
+  for (uint64_t qi = uint64_t(blockIdx.x) * kGetWaves + wave_id(); qi < a.nq; qi += stride) {
+    uint32_t status = LSMBLK_SCAN_EMPTY, b0 = kNone, e0 = kNone, b1 = kNone, e1 = kNone, nb = 0;
+    do {
+      const uint32_t s = uni(a.q_sst[qi]), bnd = uni(a.q_bound[qi]);
+      const uint32_t lk = bnd & 3, uk = (bnd >> 2) & 3;
+      if (s >= a.nsst || lk == 3 || uk == 3) {
+        err |= LSMBLK_ERR_SEGMENTS;
+        break;
+      }
+      uint32_t l0 = 0, l1 = 0, u0 = 0, u1 = 0;
+      if (lk) {
+        l0 = uni(a.lkey_off[qi]);
+        l1 = uni(a.lkey_off[qi + 1]);
+      }
+      if (uk) {
+        u0 = uni(a.ukey_off[qi]);
+        u1 = uni(a.ukey_off[qi + 1]);
+      }
+      if ((lk && l1 <= l0) || (uk && u1 <= u0)) {
+        err |= LSMBLK_ERR_EMPTY_KEY;
+        break;
+      }
+      // (an unbounded side: an empty descriptor, never read)
+      const QKey lo{make_rsrc_exact(const_cast<uint8_t*>(a.lkeys - llead), lk ? (llead + l1 + 3) & ~3u : 0u), llead + l0, l1 - l0};
+      const QKey up{make_rsrc_exact(const_cast<uint8_t*>(a.ukeys - ulead), uk ? (ulead + u1 + 3) & ~3u : 0u), ulead + u0, u1 - u0};
+      const lsmblk_sst_desc* dp = a.desc + s;
+      const uint32_t nblk = uni(dp->nblk), mo = uni(dp->meta_offset);
+      if (nblk == 0) break;  // not opened
+      const uint8_t* const F = a.files + uni64(a.file_off[s]);
+      const lsmblk_sst_index* const ix = a.index + uni(dp->blk0);
+      if (filter) {  // range_overlap (lsm_storage.rs:142-167)
+        uint32_t lcp;
+        bool outside = false;
+        if (uk) {
+          const uint8_t* fk = a.files + uni64(dp->first_key_pos);
+          const int c = wave_cmp([&](uint32_t i) { return uint32_t(fk[i]); }, uni(dp->first_key_len), up, lcp);
+          outside = uk == LSMBLK_BOUND_EXCLUDED ? c >= 0 : c > 0;  // upper <= / < the table's first key
+        }
+        if (lk && !outside) {
+          const uint8_t* lkp = a.files + uni64(dp->last_key_pos);
+          const int c = wave_cmp([&](uint32_t i) { return uint32_t(lkp[i]); }, uni(dp->last_key_len), lo, lcp);
+          outside = lk == LSMBLK_BOUND_EXCLUDED ? c <= 0 : c < 0;  // lower >= / > the table's last key
+        }
+        if (outside) {
+          status = LSMBLK_SCAN_RANGE_OUT;
+          break;
+        }
+      }
+      bool bad = false;
+      // begin
+      uint32_t b = 0, e = 0;
+      if (lk) {
+        const uint32_t P = index_partition(ix, F, nblk, lo, mvcc);
+        b = P ? P - 1 : 0;
+        uint32_t L = 0, U = 0, n = 0;
+        if (!scan_lu(F, ix, b, mo, S, lo, L, U, n)) bad = true;
+        if (!bad) {
+          e = L;
+          if (!mvcc) {  // BlockIterator::seek_to_key's probe sequence replayed on L / U (visit_block)
+            uint32_t x = 0, y = n;
+            bool found = false;
+            while (x < y && !found) {
+              const uint32_t mid = x + (y - x) / 2;
+              if (mid < L) x = mid + 1;
+              else if (mid >= U) y = mid;
+              else {
+                e = mid;
+                found = true;
+              }
+            }
+            if (!found) e = x;
+          }
+          if (lk == LSMBLK_BOUND_INCLUDED) {
+            if (e >= n) {  // the spill
+              ++b;
+              e = 0;
+            }
+          } else {
+            // forward while the entry's key equals the bound: inside [L, U) to U, from a block's end
+            // to the next block's entry 0 (at most nblk blocks)
+            for (;;) {
+              if (e >= L && e < U) e = U;
+              if (e < n) break;
+              ++b;
+              e = 0;
+              if (b >= nblk) break;
+              if (!scan_lu(F, ix, b, mo, S, lo, L, U, n)) {
+                bad = true;
+                break;
+              }
+              if (n == 0) continue;
+              if (!(L == 0 && U > 0)) break;
+            }
+          }
+        }
+      }
+      // end: the first entry with key > upper (Included) / >= upper (Excluded), not before begin
+      uint32_t eb = nblk, ee = 0;
+      if (uk && !bad) {
+        const bool strict = uk == LSMBLK_BOUND_EXCLUDED;
+        const uint32_t P = index_partition(ix, F, nblk, up, strict);
+        eb = P ? P - 1 : 0;
+        uint32_t L = 0, U = 0, n = 0;
+        if (!scan_lu(F, ix, eb, mo, S, up, L, U, n)) bad = true;
+        ee = strict ? L : U;
+        if (ee >= n) {
+          ++eb;
+          ee = 0;
+        }
+      }
+      if (bad) {
+        err |= LSMBLK_ERR_MALFORMED;
+        break;
+      }
+      if (b > nblk) b = nblk;
+      if (eb < b || (eb == b && ee < e)) {
+        eb = b;
+        ee = e;
+      }
+      b0 = b;
+      e0 = e;
+      b1 = eb;
+      e1 = ee;
+      nb = (b1 == b0 && e1 == e0) ? 0u : b1 - b0 + (e1 > 0 ? 1u : 0u);
+    } while (false);
+    if (l == 0) {
+      lsmblk_scan_result r;
+      r.status = status;
+      r.blk0 = b0;
+      r.ent0 = e0;
+      r.blk1 = b1;
+      r.ent1 = e1;
+      r.blocks = nb;
+      r.n = 0;
+      a.res[qi] = r;
+      a.qbad[qi] = 0;
+    }
+  }
+  raise_err(a.stats, err);
+}
+
+// thread t's contiguous share [x0, x1) of n items over the kScanWg threads of a workgroup
+__device__ __forceinline__ void share1024(uint64_t n, uint64_t& x0, uint64_t& x1) {
+  const uint64_t per = (n + kScanWg - 1) / kScanWg, t = threadIdx.x;
+  x0 = per * t < n ? per * t : n;
+  x1 = x0 + per < n ? x0 + per : n;
+}
+// exclusive prefix of v over the workgroup's 1024 threads, and the total
+__device__ __forceinline__ uint64_t block_excl1024(uint64_t v, uint64_t* wsum, uint64_t& tot) {
+  static_assert(kScanWg == 1024, "16 wave sums");
+  const uint32_t w = threadIdx.x >> 6;
+  const uint64_t inc = wave_incl_scan<uint64_t>(v);
+  __syncthreads();  // wsum's previous use is over
+  if (lane_id() == 63) wsum[w] = inc;
+  __syncthreads();
+  uint64_t base = 0;
+  tot = 0;
+  for (uint32_t x = 0; x < 16; ++x) {
+    if (x < w) base += wsum[x];
+    tot += wsum[x];
+  }
+  return base + inc - v;
+}
+
+__global__ __launch_bounds__(kScanWg) void scan_units_kernel(ScanArgs a) {
+  __shared__ uint64_t wsum[16];
+  uint64_t q0, q1;
+  share1024(a.nq, q0, q1);
+  uint64_t sum = 0, tot;
+  for (uint64_t q = q0; q < q1; ++q) sum += a.res[q].blocks;
+  (void)block_excl1024(sum, wsum, tot);
+  const uint64_t bpu = tot > a.budget ? (tot + a.budget - 1) / a.budget : 1;
+  sum = 0;
+  for (uint64_t q = q0; q < q1; ++q) sum += (a.res[q].blocks + bpu - 1) / bpu;
+  uint64_t o = block_excl1024(sum, wsum, tot);
+  for (uint64_t q = q0; q < q1; ++q) {
+    a.ubase[q] = uint32_t(o);
+    o += (a.res[q].blocks + bpu - 1) / bpu;
+  }
+  if (threadIdx.x == 0) {
+    a.ubase[a.nq] = uint32_t(tot);  // <= nq + budget < 2^32
+    a.hdr[0] = tot;
+    a.hdr[1] = bpu;
+  }
+}
+
+// the range of unit u: the last q with ubase[q] <= u (empty ranges share their successor's base)
+__device__ __forceinline__ uint32_t unit_query(const uint32_t* ubase, uint64_t nq, uint32_t u) {
+  return kary_first_false(0, uint32_t(nq) + 1, [&](uint32_t i) { return ubase[i] <= u; }) - 1;
+}
+
+// One unit's blocks: fn(image, header, block, first entry, end entry) per block, in order; false as
+// soon as a block is malformed.
+template <class Fn>
+__device__ __forceinline__ bool unit_blocks(const ScanArgs& a, uint32_t q, uint32_t u, uint8_t* S, Fn fn) {
+  const uint32_t s = uni(a.q_sst[q]);
+  const lsmblk_sst_desc* dp = a.desc + s;
+  const uint8_t* const F = a.files + uni64(a.file_off[s]);
+  const lsmblk_sst_index* const ix = a.index + uni(dp->blk0);
+  const uint32_t mo = uni(dp->meta_offset), nblk = uni(dp->nblk);
+  const uint32_t b0 = uni(a.res[q].blk0), e0 = uni(a.res[q].ent0), b1 = uni(a.res[q].blk1), e1 = uni(a.res[q].ent1);
+  const uint32_t nb = uni(a.res[q].blocks), bpu = uint32_t(uni64(a.hdr[1]));
+  const uint64_t first = uint64_t(u - uni(a.ubase[q])) * bpu;
+  for (uint64_t j = first; j < first + bpu && j < nb; ++j) {
+    const uint32_t b = b0 + uint32_t(j);
+    if (b >= nblk) return false;
+    const bool ok = on_block(F, ix, b, mo, S, [&](const auto& im, uint32_t len) {
+      const BlkHdr h = get_hdr(im, len);
+      if (!h.ok) return false;
+      const uint32_t w0 = b == b0 ? e0 : 0u, w1 = b == b1 ? e1 : h.n;
+      return fn(im, h, w0, w1 < h.n ? w1 : h.n);
+    });
+    if (!ok) return false;
+  }
+  return true;
+}
+
+__global__ __launch_bounds__(64 * kGetWaves) void scan_count_kernel(ScanArgs a) {
+  __shared__ __attribute__((aligned(16))) uint8_t img[kGetWaves][kGetImg];
+  const uint32_t l = lane_id();
+  uint8_t* const S = img[wave_id()];
+  const uint64_t nu = uni64(a.hdr[0]), stride = uint64_t(gridDim.x) * kGetWaves;
+  uint32_t err = 0;
+  for (uint64_t u = uint64_t(blockIdx.x) * kGetWaves + wave_id(); u < nu; u += stride) {
+    const uint32_t q = unit_query(a.ubase, a.nq, uint32_t(u));
+    uint64_t ne = 0, kb = 0, vb = 0;
+    const bool ok = unit_blocks(a, q, uint32_t(u), S, [&](const auto& im, const BlkHdr& h, uint32_t w0, uint32_t w1) {
+      bool bad = false;
+      for (uint32_t c = 0; c < h.n; c += 64) {  // every entry is checked, the window's are counted
+        const uint32_t e = c + l;
+        if (e < h.n) {
+          uint32_t off = 0, pf = 0, sf = 0, vl = 0;
+          if (!parse_entry(im, h, e, off, pf, sf, vl)) {
+            bad = true;
+          } else if (e >= w0 && e < w1) {
+            ne += 1;
+            kb += pf + sf;
+            vb += vl;
+          }
+        }
+      }
+      return __ballot(bad) == 0;
+    });
+    if (!ok) {
+      err |= LSMBLK_ERR_MALFORMED;
+      if (l == 0) a.qbad[q] = 1;
+    }
+    ne = wave_sum<uint64_t>(ne);
+    kb = wave_sum<uint64_t>(kb);
+    vb = wave_sum<uint64_t>(vb);
+    if (l == 0) {
+      a.ucnt[3 * u] = ne;
+      a.ucnt[3 * u + 1] = kb;
+      a.ucnt[3 * u + 2] = vb;
+    }
+  }
+  raise_err(a.stats, err);
+}
+
+__global__ __launch_bounds__(kScanWg) void scan_offsets_kernel(ScanArgs a) {
+  __shared__ uint64_t wsum[16];
+  const uint64_t nu = a.hdr[0];
+  uint64_t u0, u1;
+  share1024(nu, u0, u1);
+  // a share's first range by search, then forward with the units (ubase is non-decreasing)
+  auto first_query = [&](uint64_t u) {
+    uint64_t lo = 0, hi = a.nq;  // the last q with ubase[q] <= u
+    while (lo < hi) {
+      const uint64_t mid = (lo + hi + 1) / 2;
+      if (a.ubase[mid] <= u) lo = mid;
+      else hi = mid - 1;
+    }
+    return lo;
+  };
+  // only a batch with a malformed block follows the units' ranges (dependent loads per unit);
+  // otherwise a share is a run of independent loads
+  const bool masked = (a.stats[3] & LSMBLK_ERR_MALFORMED) != 0;
+  uint64_t sum[3] = {0, 0, 0}, tot[3], base[3];
+  if (u0 < u1 && masked) {
+    uint64_t q = first_query(u0);
+    for (uint64_t u = u0; u < u1; ++u) {
+      while (q + 1 < a.nq && a.ubase[q + 1] <= u) ++q;
+      if (!a.qbad[q])
+        for (uint32_t k = 0; k < 3; ++k) sum[k] += a.ucnt[3 * u + k];
+    }
+  } else {
+    for (uint64_t u = u0; u < u1; ++u)
+      for (uint32_t k = 0; k < 3; ++k) sum[k] += a.ucnt[3 * u + k];
+  }
+  for (uint32_t k = 0; k < 3; ++k) base[k] = block_excl1024(sum[k], wsum, tot[k]);
+  if (!masked) {
+    for (uint64_t u = u0; u < u1; ++u)
+      for (uint32_t k = 0; k < 3; ++k) {
+        const uint64_t v = a.ucnt[3 * u + k];
+        a.ucnt[3 * u + k] = base[k];
+        base[k] += v;
+      }
+  } else if (u0 < u1) {
+    uint64_t q = first_query(u0);
+    for (uint64_t u = u0; u < u1; ++u) {
+      while (q + 1 < a.nq && a.ubase[q + 1] <= u) ++q;
+      const bool live = !a.qbad[q];
+      for (uint32_t k = 0; k < 3; ++k) {
+        const uint64_t v = a.ucnt[3 * u + k];
+        a.ucnt[3 * u + k] = base[k];
+        if (live) base[k] += v;
+      }
+    }
+  }
+  if (threadIdx.x == 0) {
+    uint32_t e = 0;
+    for (uint32_t k = 0; k < 3; ++k) {
+      a.stats[k] = tot[k];
+      if (tot[k] > 0xFFFFFFFFull) e |= LSMBLK_ERR_OVERFLOW;
+    }
+    if (a.has_out && (tot[0] > a.entry_cap || tot[1] > a.key_cap || tot[2] > a.val_cap)) e |= LSMBLK_ERR_CAPACITY;
+    if (a.has_out && !e) {
+      a.okey_off[tot[0]] = uint32_t(tot[1]);
+      a.oval_off[tot[0]] = uint32_t(tot[2]);
+    }
+    if (e) atomicOr(reinterpret_cast<unsigned long long*>(a.stats + 3), (unsigned long long)e);
+  }
+  __threadfence_block();
+  __syncthreads();  // the unit prefixes are written
+  for (uint64_t q = threadIdx.x; q <= a.nq; q += kScanWg) {
+    const uint32_t ub = a.ubase[q];
+    const uint64_t st = ub < nu ? a.ucnt[3 * uint64_t(ub)] : tot[0];
+    a.seg_start[q] = uint32_t(st);
+    if (q < a.nq) {
+      const uint32_t ue = a.ubase[q + 1];
+      const uint64_t n = (ue < nu ? a.ucnt[3 * uint64_t(ue)] : tot[0]) - st;
+      lsmblk_scan_result r = a.res[q];
+      if (a.qbad[q]) {
+        r.blk0 = r.ent0 = r.blk1 = r.ent1 = kNone;
+        r.blocks = 0;
+      }
+      r.n = n;
+      if (r.status != LSMBLK_SCAN_RANGE_OUT) r.status = n ? LSMBLK_SCAN_OK : LSMBLK_SCAN_EMPTY;
+      a.res[q] = r;
+    }
+  }
+}
+
+// len bytes of the image from src -> dst by the 16 lanes of a quarter wave (sub = lane & 15), any
+// alignment: 16-B pieces, then the last partial piece one byte per lane (adjacent lanes, adjacent
+// bytes: one store instruction; a serial byte loop in one lane cost a round trip per byte, and most
+// keys' prefix and suffix are shorter than 16 bytes).
+template <class Img>
+__device__ __forceinline__ void quarter_copy(uint8_t* dst, const Img& im, uint32_t src, uint32_t len, uint32_t sub) {
+  const uint32_t full = len & ~15u;
+  for (uint32_t o = 16 * sub; o < full; o += 256) {
+    const u32x4 v{im.le32(src + o), im.le32(src + o + 4), im.le32(src + o + 8), im.le32(src + o + 12)};
+    *reinterpret_cast<u32x4*>(dst + o) = v;
+  }
+  const uint32_t x = full + sub;
+  if (x < len) dst[x] = uint8_t(im.u8(src + x));
+}
+
+__global__ __launch_bounds__(64 * kGetWaves) void scan_emit_kernel(ScanArgs a) {
+  __shared__ __attribute__((aligned(16))) uint8_t img[kGetWaves][kGetImg];
+  if (a.stats[3] & (LSMBLK_ERR_CAPACITY | LSMBLK_ERR_OVERFLOW)) return;
+  const uint32_t l = lane_id(), sub = l & 15, grp = l >> 4;
+  uint8_t* const S = img[wave_id()];
+  const uint64_t nu = uni64(a.hdr[0]), stride = uint64_t(gridDim.x) * kGetWaves;
+  for (uint64_t u = uint64_t(blockIdx.x) * kGetWaves + wave_id(); u < nu; u += stride) {
+    const uint32_t q = unit_query(a.ubase, a.nq, uint32_t(u));
+    if (uni(a.qbad[q])) continue;
+    uint64_t ei = uni64(a.ucnt[3 * u]), ko = uni64(a.ucnt[3 * u + 1]), vo = uni64(a.ucnt[3 * u + 2]);
+    (void)unit_blocks(a, q, uint32_t(u), S, [&](const auto& im, const BlkHdr& h, uint32_t w0, uint32_t w1) {
+      for (uint32_t c = w0; c < w1; c += 64) {
+        const uint32_t e = c + l, cnt = w1 - c < 64 ? w1 - c : 64u;
+        uint32_t off = 0, pf = 0, sf = 0, vl = 0;
+        bool live = e < w1 && parse_entry(im, h, e, off, pf, sf, vl);
+        const uint32_t kl = live ? pf + sf : 0u;
+        if (!live) vl = 0;
+        const uint32_t ik = wave_incl_scan32(kl), iv = wave_incl_scan32(vl);
+        const uint64_t mk = ko + ik - kl, mv = vo + iv - vl;  // this entry's key / value place
+        // (the totals passed the capacity check; a place past a capacity would be a block that
+        // changed since the count: such an entry is not written)
+        live = live && ei + l < a.entry_cap && mk + kl <= a.key_cap && mv + vl <= a.val_cap;
+        if (live) {
+          a.okey_off[ei + l] = uint32_t(mk);
+          a.oval_off[ei + l] = uint32_t(mv);
+          a.ots[ei + l] = im.u64(off + 4 + sf);
+        }
+        for (uint32_t r = 0; r < cnt; r += 4) {  // four entries a round, 16 lanes each
+          const uint32_t t = r + grp;
+          const bool on = __shfl(live ? 1 : 0, t, 64) != 0 && t < cnt;
+          const uint32_t xoff = __shfl(off, t, 64), xpf = __shfl(pf, t, 64), xsf = __shfl(sf, t, 64);
+          const uint32_t xvl = __shfl(vl, t, 64);
+          const uint32_t xk = __shfl(uint32_t(mk), t, 64), xv = __shfl(uint32_t(mv), t, 64);
+          if (on) {
+            quarter_copy(a.okeys + xk, im, 4, xpf, sub);  // first_key[..prefix]
+            quarter_copy(a.okeys + xk + xpf, im, xoff + 4, xsf, sub);
+            quarter_copy(a.ovals + xv, im, xoff + 14 + xsf, xvl, sub);
+          }
+        }
+        ei += cnt;
+        ko += uint32_t(__builtin_amdgcn_readlane(ik, 63));
+        vo += uint32_t(__builtin_amdgcn_readlane(iv, 63));
+      }
+      return true;
+    });
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -771,6 +1314,79 @@ int lsmblk_sst_get_batch(lsmblk_ctx* c, const uint8_t* files, const uint64_t* fi
     const uint64_t gw = (nq + 3) / 4;
     LSM_LAUNCH(val_gather_kernel, dim3(uint32_t(gw < cap ? gw : cap)), dim3(256), 0, st, a);
   }
+  return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
+}
+
+int lsmblk_sst_scan_batch(lsmblk_ctx* c, const uint8_t* files, const uint64_t* file_off, uint32_t nsst,
+                          const lsmblk_sst_desc* desc, const lsmblk_sst_index* index, const uint32_t* q_sst,
+                          const uint8_t* lkeys, const uint32_t* lkey_off, const uint8_t* ukeys, const uint32_t* ukey_off,
+                          const uint32_t* q_bound, uint64_t nq, uint32_t flags, lsmblk_scan_result* res,
+                          const lsmblk_kv_stream* out, uint32_t* seg_start, uint64_t* stats, void* stream) {
+  if (!c || !stats || !seg_start || (flags & ~(LSMBLK_SCAN_NO_FILTER | LSMBLK_SCAN_MVCC))) return LSMBLK_E_INVAL;
+  if (nq && (!q_sst || !q_bound || !lkey_off || !ukey_off || !res || (nsst && (!files || !file_off || !desc))))
+    return LSMBLK_E_INVAL;
+  if (out && (!out->key_off || !out->val_off || (out->entry_cap && !out->ts) || (out->key_cap && !out->keys) ||
+              (out->val_cap && !out->vals)))
+    return LSMBLK_E_INVAL;
+  if ((reinterpret_cast<uintptr_t>(files) & 15) || (reinterpret_cast<uintptr_t>(index) & 15) || nq > 0x7FFFFFFFull)
+    return LSMBLK_E_INVAL;
+  std::lock_guard<std::mutex> g(c->mu);
+  DeviceGuard dg(c->device, c);
+  if (!dg.ok) return LSMBLK_E_HIP;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (hipMemsetAsync(stats, 0, LSMBLK_STATS_WORDS * 8, st) != hipSuccess) return LSMBLK_E_HIP;
+  if (nq == 0) {
+    if (hipMemsetAsync(seg_start, 0, 4, st) != hipSuccess) return LSMBLK_E_HIP;
+    if (out && (hipMemsetAsync(out->key_off, 0, 4, st) != hipSuccess || hipMemsetAsync(out->val_off, 0, 4, st) != hipSuccess))
+      return LSMBLK_E_HIP;
+    return LSMBLK_OK;
+  }
+  // workspace: ubase | qbad | hdr | ucnt, sized by nq and the unit budget alone
+  const uint64_t budget = c->scan_units, units = nq + budget;
+  const uint64_t o_qbad = (4 * (nq + 1) + 255) & ~255ull, o_hdr = o_qbad + ((4 * nq + 255) & ~255ull);
+  const uint64_t o_cnt = o_hdr + 256, need = o_cnt + 24 * units;
+  int rc;
+  if (need > c->sws_cap && (rc = grow(st, &c->sws, &c->sws_cap, need, 1))) return rc;
+  ScanArgs a;
+  a.files = files;
+  a.file_off = file_off;
+  a.nsst = nsst;
+  a.desc = desc;
+  a.index = index;
+  a.q_sst = q_sst;
+  a.lkeys = lkeys;
+  a.lkey_off = lkey_off;
+  a.ukeys = ukeys;
+  a.ukey_off = ukey_off;
+  a.q_bound = q_bound;
+  a.nq = nq;
+  a.flags = flags;
+  a.res = res;
+  a.okeys = out ? out->keys : nullptr;
+  a.okey_off = out ? out->key_off : nullptr;
+  a.ovals = out ? out->vals : nullptr;
+  a.oval_off = out ? out->val_off : nullptr;
+  a.ots = out ? out->ts : nullptr;
+  a.entry_cap = out ? out->entry_cap : 0;
+  a.key_cap = out ? out->key_cap : 0;
+  a.val_cap = out ? out->val_cap : 0;
+  a.has_out = out ? 1u : 0u;
+  a.seg_start = seg_start;
+  a.ubase = reinterpret_cast<uint32_t*>(c->sws);
+  a.qbad = reinterpret_cast<uint32_t*>(c->sws + o_qbad);
+  a.hdr = reinterpret_cast<uint64_t*>(c->sws + o_hdr);
+  a.ucnt = reinterpret_cast<uint64_t*>(c->sws + o_cnt);
+  a.budget = uint32_t(budget);
+  a.stats = stats;
+  int cus = 256;
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
+  const uint64_t cap = uint64_t(cus > 0 ? cus : 256) * 8;
+  const uint64_t qw = (nq + kGetWaves - 1) / kGetWaves, uw = (units + kGetWaves - 1) / kGetWaves;
+  LSM_LAUNCH(scan_bounds_kernel, dim3(uint32_t(qw < cap ? qw : cap)), dim3(64 * kGetWaves), 0, st, a);
+  LSM_LAUNCH(scan_units_kernel, dim3(1), dim3(kScanWg), 0, st, a);
+  LSM_LAUNCH(scan_count_kernel, dim3(uint32_t(uw < cap ? uw : cap)), dim3(64 * kGetWaves), 0, st, a);
+  LSM_LAUNCH(scan_offsets_kernel, dim3(1), dim3(kScanWg), 0, st, a);
+  if (out) LSM_LAUNCH(scan_emit_kernel, dim3(uint32_t(uw < cap ? uw : cap)), dim3(64 * kGetWaves), 0, st, a);
   return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
 }
 

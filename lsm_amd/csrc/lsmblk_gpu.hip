@@ -3885,6 +3885,100 @@ __global__ __launch_bounds__(256) void filt_write_kernel(FiltArgs a) {
   }
 }
 
+// ---------------------------------------------------------------- read filter
+// lsmblk_read_filter_batch: what a reader at read_ts sees of each segment of a KV stream --
+// LsmIterator::move_to_key / next (src/lsm_iterator.rs:45-86) over an inner iterator yielding the
+// segment.  With user keys ascending and versions newest first inside a segment the loop has a
+// predecessor-only closed form (checked against a restatement of the loop, tests/test_scan_cases.py):
+//   keep = ts <= read_ts && value not empty
+//          && (the segment's first entry || key differs from the previous entry's || prev.ts > read_ts)
+// The flag kernel below has filt_flag_kernel's shape and feeds filt_scan_kernel / filt_write_kernel
+// unchanged (they read only the stream, the flags, the tile sums and the capacities of FiltArgs).
+struct ReadFiltArgs {
+  FiltArgs f;
+  const uint32_t* seg_start;  // nseg + 1
+  const uint64_t* seg_ts;     // nseg
+  uint32_t nseg;
+  uint32_t* out_seg_start;    // nseg + 1
+};
+
+__device__ __forceinline__ bool readf_keep(const ReadFiltArgs& a, uint64_t i) {
+  const FiltArgs& f = a.f;
+  // the entry's segment: the last s with seg_start[s] <= i (seg_start is sorted; empty segments
+  // share their successor's start and hold nothing)
+  uint32_t lo = 0, hi = a.nseg;
+  if (i < a.seg_start[0] || i >= a.seg_start[a.nseg]) return false;
+  while (lo < hi) {
+    const uint32_t mid = lo + (hi - lo + 1) / 2;
+    if (a.seg_start[mid] <= i) lo = mid;
+    else hi = mid - 1;
+  }
+  if (lo >= a.nseg) return false;
+  const uint64_t T = a.seg_ts[lo];
+  if (f.ts[i] > T || f.val_off[i + 1] == f.val_off[i]) return false;
+  if (i == 0 || i == a.seg_start[lo] || f.ts[i - 1] > T) return true;  // nothing is compared across a segment start
+  const uint32_t k0 = f.key_off[i], kl = f.key_off[i + 1] - k0, p0 = f.key_off[i - 1];
+  if (k0 - p0 != kl) return true;
+  bool differ = false;
+  uint32_t j = 0;
+  for (; j + 16 <= kl && !differ; j += 16) {  // unaligned 16-B compares, then bytes
+    const u32x4 x = *reinterpret_cast<const u32x4*>(f.keys + p0 + j);
+    const u32x4 y = *reinterpret_cast<const u32x4*>(f.keys + k0 + j);
+    differ = x.x != y.x || x.y != y.y || x.z != y.z || x.w != y.w;
+  }
+  for (; j < kl && !differ; ++j) differ = f.keys[p0 + j] != f.keys[k0 + j];
+  return differ;
+}
+
+__global__ __launch_bounds__(256) void readf_flag_kernel(ReadFiltArgs a) {
+  uint32_t c = 0;
+  uint64_t kb = 0, vb = 0;
+#pragma unroll
+  for (uint32_t sub = 0; sub < kFiltTile / 256; ++sub) {
+    const uint64_t i = uint64_t(blockIdx.x) * kFiltTile + sub * 256 + threadIdx.x;
+    if (i < a.f.n) {
+      const bool k = readf_keep(a, i);
+      a.f.keep[i] = k;
+      if (k) {
+        c += 1;
+        kb += a.f.key_off[i + 1] - a.f.key_off[i];
+        vb += a.f.val_off[i + 1] - a.f.val_off[i];
+      }
+    }
+  }
+  __shared__ uint64_t ws[4][3];
+  const uint32_t w = wave_id();
+  const uint32_t sc = wave_sum32(c);
+  const uint64_t sk = wave_sum<uint64_t>(kb), sv = wave_sum<uint64_t>(vb);
+  if (lane_id() == 0) ws[w][0] = sc, ws[w][1] = sk, ws[w][2] = sv;
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    const uint32_t q = threadIdx.x;
+    a.f.tile_sum[3 * uint64_t(blockIdx.x) + q] = ws[0][q] + ws[1][q] + ws[2][q] + ws[3][q];
+  }
+}
+
+// out_seg_start[s] = the kept entries before seg_start[s]: its tile's prefix plus the flags of the
+// tile's entries before it, one wave per table entry (after filt_scan_kernel).
+__global__ __launch_bounds__(256) void readf_seg_kernel(ReadFiltArgs a) {
+  const uint64_t s = uint64_t(blockIdx.x) * 4 + wave_id();
+  if (s > a.nseg) return;
+  const uint64_t p = a.seg_start[s];
+  uint32_t err = 0;
+  if (p > a.f.n || (s < a.nseg && a.seg_start[s + 1] < p)) err = LSMBLK_ERR_SEGMENTS;
+  uint64_t kept = a.f.stats[0];  // at or past the stream's end: everything kept
+  if (p < a.f.n) {
+    const uint64_t t = p / kFiltTile;
+    uint32_t c = 0;
+    for (uint64_t i = t * kFiltTile + lane_id(); i < p; i += 64) c += a.f.keep[i];
+    kept = a.f.tile_pre[3 * t] + wave_sum32(c);
+  }
+  if (lane_id() == 0) {
+    a.out_seg_start[s] = uint32_t(kept);
+    if (err) or_err(a.f.stats, err);
+  }
+}
+
 // ================================================================ host side
 namespace {
 
@@ -4060,6 +4154,8 @@ int lsmblk_debug_set(lsmblk_ctx* c, int key, uint32_t value) {
     c->fuse_on = value != 0;
   } else if (key == LSMBLK_DEBUG_PLAN_PIPE) {
     c->plan_pipe = value != 0;
+  } else if (key == LSMBLK_DEBUG_SCAN_UNITS && value <= (1u << 24)) {
+    c->scan_units = value ? value : kScanUnitsDefault;
   } else if (key == LSMBLK_DEBUG_KERNEL_TIMING) {
     if (value && !c->timing) c->klog_n = 0;  // the log restarts with the timing
     c->timing = value != 0;
@@ -4576,6 +4672,52 @@ int lsmblk_compact_filter_batch(lsmblk_ctx* c, const lsmblk_kv_stream* in, uint6
   if (ntiles) LSM_LAUNCH(filt_flag_kernel, dim3(uint32_t(ntiles)), dim3(256), 0, st, a);
   LSM_LAUNCH(filt_scan_kernel, dim3(1), dim3(1024), 0, st, a);
   if (ntiles) LSM_LAUNCH(filt_write_kernel, dim3(uint32_t(ntiles)), dim3(256), 0, st, a);
+  return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
+}
+
+int lsmblk_read_filter_batch(lsmblk_ctx* c, const lsmblk_kv_stream* in, const uint32_t* seg_start, const uint64_t* seg_ts,
+                             uint32_t nseg, const lsmblk_kv_stream* out, uint32_t* out_seg_start, uint64_t* stats,
+                             void* stream) {
+  if (!c || !in || !out || !stats || !seg_start || !out_seg_start || !out->key_off || !out->val_off) return LSMBLK_E_INVAL;
+  if ((nseg && !seg_ts) || (in->n && (!in->key_off || !in->val_off || !in->ts)) || nseg > 0x7FFFFFFFu) return LSMBLK_E_INVAL;
+  if (in->n >= 0xFFFFFFFFull) return LSMBLK_E_INVAL;
+  std::lock_guard<std::mutex> g(c->mu);
+  DeviceGuard dg(c->device, c);
+  if (!dg.ok) return LSMBLK_E_HIP;
+  const uint64_t n = in->n, ntiles = (n + kFiltTile - 1) / kFiltTile;
+  int rc;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if ((rc = grow(st, &c->filt_keep, &c->filt_cap, n + 1, 1))) return rc;
+  if ((rc = grow(st, &c->filt_tile, &c->filt_tile_cap, ntiles + 1, 6))) return rc;
+  if (hipMemsetAsync(stats, 0, LSMBLK_STATS_WORDS * 8, st) != hipSuccess) return LSMBLK_E_HIP;
+  ReadFiltArgs a;
+  memset(&a.f, 0, sizeof(a.f));
+  a.f.keys = in->keys;
+  a.f.key_off = in->key_off;
+  a.f.vals = in->vals;
+  a.f.val_off = in->val_off;
+  a.f.ts = in->ts;
+  a.f.n = n;
+  a.f.okeys = out->keys;
+  a.f.okey_off = out->key_off;
+  a.f.ovals = out->vals;
+  a.f.oval_off = out->val_off;
+  a.f.ots = out->ts;
+  a.f.entry_cap = out->entry_cap;
+  a.f.key_cap = out->key_cap;
+  a.f.val_cap = out->val_cap;
+  a.f.keep = c->filt_keep;
+  a.f.tile_sum = c->filt_tile;
+  a.f.tile_pre = c->filt_tile + 3 * c->filt_tile_cap;
+  a.f.stats = stats;
+  a.seg_start = seg_start;
+  a.seg_ts = seg_ts;
+  a.nseg = nseg;
+  a.out_seg_start = out_seg_start;
+  if (ntiles) LSM_LAUNCH(readf_flag_kernel, dim3(uint32_t(ntiles)), dim3(256), 0, st, a);
+  LSM_LAUNCH(filt_scan_kernel, dim3(1), dim3(1024), 0, st, a.f);
+  LSM_LAUNCH(readf_seg_kernel, dim3(nseg / 4 + 1), dim3(256), 0, st, a);
+  if (ntiles) LSM_LAUNCH(filt_write_kernel, dim3(uint32_t(ntiles)), dim3(256), 0, st, a.f);
   return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
 }
 

@@ -11,7 +11,9 @@
                     with the read_block CRC check (lsmblk_decode_batch_ex)
   SstSet            SST files resident in device memory, opened once on the device
                     (lsmblk_sst_open_batch), answering batches of (sst, key, read_ts) point lookups
-                    with the entry and its value (lsmblk_sst_get_batch)
+                    with the entry and its value (lsmblk_sst_get_batch), and batches of
+                    (sst, lower, upper) range scans with every version in range
+                    (lsmblk_sst_scan_batch), filtered to a reader's view by batch.read_filter
 
 Device work goes through liblsmblk.so; the footer / section parsing here is host logic that mirrors
 the reference's own (the CRC-32 of those small sections is zlib's, which is crc32fast's).
@@ -23,8 +25,9 @@ import numpy as np
 import torch
 
 from . import batch
-from ._lib import (LSMBLK_E_CAPACITY, LSMBLK_GET_FOUND, LSMBLK_GET_MVCC, LSMBLK_GET_NO_FILTER, GetResultC, LsmBlkError,
-                   SstDescC, SstIndexC, check, lib)
+from ._lib import (LSMBLK_BOUND_EXCLUDED, LSMBLK_BOUND_INCLUDED, LSMBLK_BOUND_UNBOUNDED, LSMBLK_E_CAPACITY,
+                   LSMBLK_GET_FOUND, LSMBLK_GET_MVCC, LSMBLK_GET_NO_FILTER, LSMBLK_SCAN_MVCC, LSMBLK_SCAN_NO_FILTER,
+                   GetResultC, LsmBlkError, ScanResultC, SstDescC, SstIndexC, check, lib)
 
 
 class MemTable:
@@ -219,6 +222,12 @@ class SsTable:
 
 ERR_CAPACITY = 2  # LSMBLK_ERR_CAPACITY
 GET_FIELDS = ("status", "blk", "ent", "hit_blk", "hit_ent", "vlen", "ts", "val_pos")
+SCAN_FIELDS = ("status", "blk0", "ent0", "blk1", "ent1", "blocks", "n")
+BOUND_KINDS = {"unbounded": LSMBLK_BOUND_UNBOUNDED, "included": LSMBLK_BOUND_INCLUDED, "excluded": LSMBLK_BOUND_EXCLUDED}
+
+
+def _bound_kind(k):
+    return BOUND_KINDS[k] if isinstance(k, str) else int(k)
 
 
 class SstSet:
@@ -387,3 +396,82 @@ class SstSet:
             out["values"] = [hv[vo[i]:vo[i + 1]].tobytes() if r["status"][i] == LSMBLK_GET_FOUND else None
                              for i in range(len(keys))]
         return out
+
+    # ---- range scans
+    def scan_into(self, q_sst, lkeys, lkey_off, ukeys, ukey_off, q_bound, nq, flags, res, seg_start, stats,
+                  out: batch.KVStream = None, caps=None):
+        """Asynchronous lsmblk_sst_scan_batch over device tensors (no host sync): q_sst / lkey_off /
+        ukey_off / q_bound / seg_start int32 (u32), res uint8[32 nq], stats int64[4]; out None: res,
+        seg_start and the sizes in stats only; caps = (entry_cap, key_cap, val_cap), default out.caps()."""
+        dev = self.device.index
+        batch._need(q_sst, torch.int32, "q_sst", dev, nq)
+        batch._need(lkey_off, torch.int32, "lkey_off", dev, nq + 1)
+        batch._need(ukey_off, torch.int32, "ukey_off", dev, nq + 1)
+        batch._need(q_bound, torch.int32, "q_bound", dev, nq)
+        batch._need(res, torch.uint8, "res", dev, nq * ctypes.sizeof(ScanResultC))
+        batch._need(seg_start, torch.int32, "seg_start", dev, nq + 1)
+        batch._need(stats, torch.int64, "stats", dev, batch.STATS_WORDS)
+        co = None
+        if out is not None:
+            out.check(dev, "out", 0)
+            co = out._c(*(caps if caps is not None else out.caps()))
+        batch._native("lsmblk_sst_scan_batch", dev, self.stream, batch._ptr(self.files), self.file_off.data_ptr(),
+                      self.nsst, self.desc_t.data_ptr(), batch._ptr(self.index_t), q_sst.data_ptr(), lkeys.data_ptr(),
+                      lkey_off.data_ptr(), ukeys.data_ptr(), ukey_off.data_ptr(), q_bound.data_ptr(), nq, flags,
+                      res.data_ptr(), ctypes.byref(co) if co is not None else None, seg_start.data_ptr(),
+                      stats.data_ptr(), batch._stream_ptr(self.stream, dev))
+
+    def upload_ranges(self, q_sst, lower, upper, lower_kind, upper_kind):
+        """Host ranges -> the device tensors of scan_into: (q_sst, lkeys, lkey_off, ukeys, ukey_off,
+        q_bound).  A kind is one per range or one for all: "unbounded" / "included" / "excluded" or
+        LSMBLK_BOUND_*; an unbounded side's key may be None."""
+        nq = len(lower)
+        kinds = lambda k: [_bound_kind(x) for x in k] if isinstance(k, (list, tuple, np.ndarray)) else [_bound_kind(k)] * nq
+        bnd = np.array([a | (b << 2) for a, b in zip(kinds(lower_kind), kinds(upper_kind))] or [0], np.uint32)
+        qs, lk, lo, _ = self.upload_queries(q_sst, [k or b"" for k in lower], 0)
+        _, uk, uo, _ = self.upload_queries(q_sst, [k or b"" for k in upper], 0)
+        return qs, lk, lo, uk, uo, batch._u32_table(bnd, self.device)
+
+    def scan_raw(self, q_sst, lower, upper, lower_kind, upper_kind, flags=0, caps=None, out=None):
+        """One lsmblk_sst_scan_batch call -> (results as a numpy record array, seg_start numpy, the
+        KVStream or None, stats list); nothing raises on the stats.  caps = (entries, key bytes, value
+        bytes) of a fresh output stream (or of `out`, a caller's stream); None: sizes only."""
+        dev, nq = self.device, len(lower)
+        t = self.upload_ranges(q_sst, lower, upper, lower_kind, upper_kind)
+        res = torch.zeros(max(nq, 1) * ctypes.sizeof(ScanResultC), dtype=torch.uint8, device=dev)
+        seg = torch.zeros(nq + 1, dtype=torch.int32, device=dev)
+        stats = torch.zeros(batch.STATS_WORDS, dtype=torch.int64, device=dev)
+        if caps is not None and out is None:
+            out = batch.KVStream.empty(*caps, dev)
+        self.scan_into(*t, nq, flags, res, seg, stats, out if caps is not None else None, caps)
+        torch.cuda.synchronize(dev)
+        r = res.cpu().numpy().view(np.dtype(ScanResultC))[:nq]
+        st = [int(x) & 0xFFFFFFFFFFFFFFFF for x in stats.cpu().tolist()]
+        if caps is not None and not st[3] & (ERR_CAPACITY | 4):
+            out.n = st[0]
+        return r, seg.cpu().numpy().view(np.uint32), (out if caps is not None else None), st
+
+    def scan(self, q_sst, lower, upper, *, lower_kind, upper_kind, read_ts=None, no_filter=False, mvcc=False):
+        """Batched range scans: range i = SST q_sst[i], (lower[i], upper[i]) with the bound kinds ->
+        (dict of numpy arrays: status, blk0, ent0, blk1, ent1, blocks, n; LSMBLK_SCAN_* statuses, and
+        per range the list of (key, ts, value)).  read_ts None: every version in range (the raw scan);
+        else what a reader at read_ts (one for all, or one per range) sees of each range
+        (lsmblk_read_filter_batch).  Retries once on CAPACITY with the reported sizes."""
+        flags = (LSMBLK_SCAN_NO_FILTER if no_filter else 0) | (LSMBLK_SCAN_MVCC if mvcc else 0)
+        nq = len(lower)
+        caps = (64 * nq + 1024, 1024 * nq + 4096, 4096 * nq + 4096)
+        for _ in range(2):
+            r, seg, kv, st = self.scan_raw(q_sst, lower, upper, lower_kind, upper_kind, flags, caps)
+            if st[3] == ERR_CAPACITY:
+                caps = (st[0], st[1], st[2])
+                continue
+            break
+        if st[3]:
+            raise LsmBlkError(lib().lsmblk_stats_status(st[3]), "sst scan")
+        if read_ts is not None and nq:
+            kv, seg = batch.read_filter(kv, seg, read_ts, self.stream)
+        keys, ko, vals, vo, ts = kv.to_numpy()
+        kb, vb = keys.tobytes(), vals.tobytes()
+        rows = [[(kb[ko[i]:ko[i + 1]], int(ts[i]), vb[vo[i]:vo[i + 1]]) for i in range(int(seg[q]), int(seg[q + 1]))]
+                for q in range(nq)]
+        return {f: r[f].copy() for f in SCAN_FIELDS}, rows
