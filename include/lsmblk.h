@@ -545,7 +545,8 @@ int lsmblk_bloom_may_contain(const uint8_t* filter, size_t nbytes, uint32_t k, u
  * (lsmblk_sst_get_batch).
  * Not part of these calls: the per-block CRC of read_block (src/table.rs:226-230) -- callers verify
  * a loaded file with lsmblk_crc32_batch or lsmblk_decode_batch_ex(LSMBLK_DECODE_VERIFY_CRC) -- and
- * merging results across SSTs or levels (the caller orders its candidate SSTs). */
+ * merging results across SSTs or levels (the caller orders its candidate SSTs; lsmblk_lsm_get_batch
+ * below is the read over a whole LSM view). */
 
 /* One opened SST (64 bytes).  Positions are absolute byte offsets in `files` unless noted. */
 typedef struct {
@@ -639,6 +640,79 @@ int lsmblk_sst_get_batch(lsmblk_ctx* ctx, const uint8_t* files, const uint64_t* 
                          const lsmblk_sst_desc* desc, const lsmblk_sst_index* index, const uint32_t* q_sst,
                          const uint8_t* qkeys, const uint32_t* qkey_off, const uint64_t* q_ts, uint64_t nq,
                          uint32_t flags, lsmblk_get_result* res, uint8_t* vals, uint64_t val_cap,
+                         uint32_t* val_off, uint64_t* stats, void* stream);
+
+/* ------------------------------------------------------------------ LSM point reads (device) */
+/* LsmStorageInner::get_with_ts (src/lsm_storage.rs:361-439) below the memtables, for a batch of keys
+ * over an LSM view of the opened set: every L0 table in order, per level the one table whose key
+ * range holds the key, keep_table (key_within, then the bloom test) on each, the merge, the reader's
+ * view at read_ts, `key == query && !value.is_empty()`.  The memtables stay on the host.
+ *
+ * Sources, in priority order: source i < nl0 is table l0[i] (l0_sstables order = MergeIterator::
+ * create's index order); source nl0 + l is level l, whose tables are in key order and do not overlap
+ * (SstConcatIterator::check_sst_valid, src/iterators/concat_iterator.rs:82-93).  A level's source
+ * for a key is the last table of the level with first_key <= key, which must then pass
+ * key <= last_key and the bloom test like an L0 table; a key below the level's first table, above
+ * its last or in a gap between two tables has no source in that level.
+ *
+ * The merge is MergeIterator's (LSMBLK_MERGE_RUNS, the default everywhere in this library): Key's
+ * Eq / Ord ignore the ts (src/key.rs:63-81), and when MergeIterator::next leaves a key it moves
+ * every other source past all of that key's versions.  In closed form: the answer comes from the
+ * first source in priority order whose landing entry's key equals the query (the decider); its
+ * versions are walked from its landing exactly as lsmblk_sst_get_batch walks them (forward while
+ * ts > read_ts), and the result is that lookup's FOUND / TOMBSTONE / ABSENT.  Sources after the
+ * decider are never consulted, even when the decider holds no visible version and a later source
+ * does; a source that lands on another key (a bloom false positive, a key inside the range that the
+ * table does not hold) decides nothing; no source on the key: ABSENT.  The as-written
+ * TwoMergeIterator nesting of get_with_ts (LSMBLK_MERGE_TWO_LEVEL) is NOT reproduced: it ends with
+ * its second iterator, so it yields nothing whenever no level table passes the filter, and differs
+ * from the above on about 15 % of random queries. */
+typedef struct {            /* all device pointers */
+  const uint32_t* l0;           /* u32[nl0]: SST ids, priority order */
+  uint32_t nl0;
+  uint32_t nlevel;
+  const uint32_t* level_sst;    /* u32[level_start[nlevel]]: per level its SST ids in key order */
+  const uint32_t* level_start;  /* u32[nlevel+1], [0] = 0, non-decreasing; an empty level is allowed */
+} lsmblk_lsm_view;
+
+/* Result of one key (48 bytes). */
+typedef struct {
+  uint32_t status;              /* LSMBLK_GET_ABSENT / FOUND / TOMBSTONE */
+  uint32_t src, sst;            /* the deciding source's ordinal and SST id (NEWEST: the chosen version's);
+                                   0xFFFFFFFF both: no source landed on the key (NEWEST: no visible version) */
+  uint32_t hit_blk, hit_ent;    /* as lsmblk_get_result, SST-local; 0xFFFFFFFF unless FOUND / TOMBSTONE */
+  uint32_t vlen;
+  uint64_t ts, val_pos;
+  uint32_t seeks;               /* sources searched (passed key_within and bloom), the decider included */
+  uint32_t bloom_out;           /* sources consulted that the bloom test rejected */
+} lsmblk_lsm_get_result;
+
+/* flags: 0 = the reference landing per table (lsmblk_sst_get_batch's default) and the decider rule;
+ * LSMBLK_GET_MVCC = the corrected landing per table and the decider rule; LSMBLK_GET_NO_FILTER has
+ * no meaning across sources (LSMBLK_E_INVAL). */
+#define LSMBLK_LSM_GET_NEWEST 4u /* implies the corrected landing; every source that passes its filters is
+                                    searched and the result is the version with the largest ts <= read_ts
+                                    over all of them (equal ts: the lower source ordinal), a tombstone
+                                    giving TOMBSTONE: the snapshot read of a (key asc, ts desc) merge */
+
+/* nq keys: query q = (qkeys[qkey_off[q] .. qkey_off[q+1]), q_ts[q]) over `view` (a host struct of
+ * device pointers) of the opened set -> res[q].  vals / val_cap / val_off and stats follow
+ * lsmblk_sst_get_batch: [0] lookups (= nq) [1] FOUND [2] value bytes [3] error flags; CAPACITY
+ * carries the required bytes and nothing is written to vals; nq == 0 writes val_off[0].
+ * With the decider rule, seeks and bloom_out count the sources up to and including the decider.
+ * The view is checked on the device in the same call before any lookup runs:
+ *   SEGMENTS   an id >= nsst; level_start[0] != 0 or level_start decreases
+ *   MALFORMED  a table of the view whose open failed (desc.err != 0), or two neighbours of a level
+ *              with last_key(i) >= first_key(i+1) (check_sst_valid)
+ * and with either raised no lookup runs: every res[q] is ABSENT with src / sst / hit_* 0xFFFFFFFF,
+ * val_off is all zero, stats[3] carries the flag.  EMPTY_KEY (that key: ABSENT, no source) and
+ * MALFORMED (a block on a lookup's path breaks the decode rules, every entry of a visited block
+ * being checked: that source decides ABSENT) are as in lsmblk_sst_get_batch.  Every walk is
+ * bounded by entry, block, table and source counts.  Asynchronous; 256 B of context workspace. */
+int lsmblk_lsm_get_batch(lsmblk_ctx* ctx, const uint8_t* files, const uint64_t* file_off, uint32_t nsst,
+                         const lsmblk_sst_desc* desc, const lsmblk_sst_index* index, const lsmblk_lsm_view* view,
+                         const uint8_t* qkeys, const uint32_t* qkey_off, const uint64_t* q_ts, uint64_t nq,
+                         uint32_t flags, lsmblk_lsm_get_result* res, uint8_t* vals, uint64_t val_cap,
                          uint32_t* val_off, uint64_t* stats, void* stream);
 
 /* ------------------------------------------------------------------ SST range scans (device) */

@@ -40,6 +40,7 @@ LSMBLK_GET_RANGE_OUT = 3
 LSMBLK_GET_BLOOM_OUT = 4
 LSMBLK_GET_NO_FILTER = 1
 LSMBLK_GET_MVCC = 2
+LSMBLK_LSM_GET_NEWEST = 4
 LSMBLK_BOUND_UNBOUNDED = 0
 LSMBLK_BOUND_INCLUDED = 1
 LSMBLK_BOUND_EXCLUDED = 2
@@ -92,6 +93,17 @@ class GetResultC(ctypes.Structure):
     """lsmblk_get_result (40 bytes)."""
     _fields_ = [("status", U32), ("blk", U32), ("ent", U32), ("hit_blk", U32), ("hit_ent", U32), ("vlen", U32),
                 ("ts", U64), ("val_pos", U64)]
+
+
+class LsmViewC(ctypes.Structure):
+    """lsmblk_lsm_view (a host struct of device pointers)."""
+    _fields_ = [("l0", P), ("nl0", U32), ("nlevel", U32), ("level_sst", P), ("level_start", P)]
+
+
+class LsmGetResultC(ctypes.Structure):
+    """lsmblk_lsm_get_result (48 bytes)."""
+    _fields_ = [("status", U32), ("src", U32), ("sst", U32), ("hit_blk", U32), ("hit_ent", U32), ("vlen", U32),
+                ("ts", U64), ("val_pos", U64), ("seeks", U32), ("bloom_out", U32)]
 
 
 class ScanResultC(ctypes.Structure):
@@ -172,6 +184,7 @@ SIGNATURES = [
     ("lsmblk_bloom_may_contain", I, [P, S, U32, U32]),
     ("lsmblk_sst_open_batch", I, [P, P, P, U32, P, P, U64, P, P]),
     ("lsmblk_sst_get_batch", I, [P, P, P, U32, P, P, P, P, P, P, U64, U32, P, P, U64, P, P, P]),
+    ("lsmblk_lsm_get_batch", I, [P, P, P, U32, P, P, ctypes.POINTER(LsmViewC), P, P, P, U64, U32, P, P, U64, P, P, P]),
     ("lsmblk_sst_scan_batch", I, [P, P, P, U32, P, P, P, P, P, P, P, P, U64, U32, P, ctypes.POINTER(KVStreamC), P, P,
                                   P]),
     ("lsmblk_read_filter_batch", I, [P, ctypes.POINTER(KVStreamC), P, P, U32, ctypes.POINTER(KVStreamC), P, P, P]),

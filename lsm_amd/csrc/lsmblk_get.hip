@@ -10,13 +10,20 @@
 //     sst_open_walk_kernel  one workgroup per SST: CRCs compared, the BlockMeta records walked over
 //                           chunks staged into LDS -> index records and the descriptor
 //   lsmblk_sst_get_batch    the lookups
-//     sst_get_kernel        one wave per lookup, grid-strided: key range, bloom probes from k lanes
+//     sst_get_kernel        one wave per lookup, grid-strided (sst_lookup): key range, bloom probes from k lanes
 //                           at once, k-ary block search over the first-key images, the landed block
 //                           staged into LDS with 16-B loads, every entry compared by its own lane
 //                           (equal range [L, U)), the reference's probe sequence replayed on L / U,
 //                           the version walk
 //     val_scan_kernel       value sizes of the FOUND lookups -> val_off (one workgroup)
 //     val_gather_kernel     one wave per FOUND lookup copies its value
+//   lsmblk_lsm_get_batch    get_with_ts below the memtables (lsm_storage.rs:381-438) for a batch of keys
+//                           over an LSM view of the opened set: L0 tables, levels, one answer per key
+//     lsm_view_check_kernel one lane per view entry: ids, failed opens, level_start, check_sst_valid
+//     lsm_get_kernel        one wave per key: lane s holds source s's table (a level's by a search over
+//                           its tables' first-key images), every lane runs keep_table for its own,
+//                           the passing sources are read in priority order by sst_lookup -- the
+//                           per-table read it shares with sst_get_kernel -- up to the decider
 //   lsmblk_sst_scan_batch   raw range scans of one SST per query (scan_with_ts's SsTableIterator per
 //                           table, lsm_storage.rs:474-502, run to its end bound); the end bound is
 //                           tested on every entry, the landing included -- LsmIterator::new's untested
@@ -351,23 +358,26 @@ __device__ __forceinline__ uint32_t kary_first_false(uint32_t lo, uint32_t hi, P
   return uni(lo + uint32_t(__builtin_popcountll(__ballot(p))));
 }
 
+// The query's leading 16 bytes as the index records hold a first key's (zero-padded, big-endian).
+__device__ __forceinline__ void query_image(const QKey& q, uint64_t& qhi, uint64_t& qlo) {
+  uint32_t w[4];
+#pragma unroll
+  for (uint32_t j = 0; j < 4; ++j) {
+    const uint32_t nv = q.len > 4 * j ? q.len - 4 * j : 0u;
+    const uint32_t v = __builtin_bswap32(q.fetch(4 * j));
+    w[j] = nv >= 4 ? v : (nv ? v & ~(~0u >> (8 * nv)) : 0u);
+  }
+  qhi = (uint64_t(w[0]) << 32) | w[1];
+  qlo = (uint64_t(w[2]) << 32) | w[3];
+}
+
 // partition_point of an SST's block first keys against the query: the blocks with first_key <= q
 // (strict: < q), by the k-ary search over the first-key images; blocks whose image equals the
 // query's, [iL, iU), compare whole keys.
 __device__ __forceinline__ uint32_t index_partition(const lsmblk_sst_index* ix, const uint8_t* F, uint32_t nblk,
                                                     const QKey& q, bool strict) {
   uint64_t qhi, qlo;
-  {
-    uint32_t w[4];
-#pragma unroll
-    for (uint32_t j = 0; j < 4; ++j) {
-      const uint32_t nv = q.len > 4 * j ? q.len - 4 * j : 0u;
-      const uint32_t v = __builtin_bswap32(q.fetch(4 * j));
-      w[j] = nv >= 4 ? v : (nv ? v & ~(~0u >> (8 * nv)) : 0u);
-    }
-    qhi = (uint64_t(w[0]) << 32) | w[1];
-    qlo = (uint64_t(w[2]) << 32) | w[3];
-  }
+  query_image(q, qhi, qlo);
   const uint32_t iL = kary_first_false(0, nblk, [&](uint32_t i) {
     const u32x4 v = *reinterpret_cast<const u32x4*>(ix + i);
     const uint64_t hi = (uint64_t(v.y) << 32) | v.x, lo = (uint64_t(v.w) << 32) | v.z;
@@ -467,6 +477,7 @@ struct Look {     // a lookup's state across the blocks it visits (wave-uniform)
   uint32_t status, blk, ent, hit_blk, hit_ent, vlen;
   uint64_t ts, val_pos;
   bool landed;
+  bool on_key;  // the landing entry's key equals the query
 };
 
 // Block b of the SST (len bytes at absolute position bpos, read through im): `first` = the block the
@@ -506,6 +517,7 @@ __device__ Visit visit_block(const Img& im, uint32_t len, uint64_t bpos, uint32_
     k.blk = b;
     k.ent = land;
     if (land < L || land >= U) return Visit{true, false};  // landed on another key
+    k.on_key = true;
     from = land;
   } else {
     if (!k.landed) {
@@ -515,6 +527,7 @@ __device__ Visit visit_block(const Img& im, uint32_t len, uint64_t bpos, uint32_
     }
     if (h.n == 0) return Visit{false, false};
     if (L != 0 || U == 0) return Visit{true, false};  // entry 0 is another key
+    k.on_key = true;  // (a spill's landing, or the walk goes on)
   }
   for (uint32_t c = from; c < U; c += 64) {
     const uint32_t e = c + l;
@@ -544,6 +557,123 @@ __device__ Visit visit_block(const Img& im, uint32_t len, uint64_t bpos, uint32_
   return Visit{U < h.n, false};
 }
 
+// The opened set a lookup reads.
+struct Opened {
+  const uint8_t* files;
+  const uint64_t* file_off;
+  const lsmblk_sst_desc* desc;
+  const lsmblk_sst_index* index;
+};
+
+struct QHash {  // fingerprint32 of the query key, computed by the first bloom test that needs it
+  uint32_t h;
+  bool valid;
+};
+
+// One table's read of one key (wave-uniform): key_within, the bloom test, find_block_idx, the landed
+// block and the blocks the iterator moves on to -> k (k.status also RANGE_OUT / BLOOM_OUT; k.on_key:
+// the landing entry's key is the query).  True: a block on the path breaks the decode rules.
+__device__ __forceinline__ bool sst_lookup(const Opened& o, uint32_t s, const QKey& q, uint64_t read_ts, bool mvcc,
+                                           bool filter, uint8_t* S, QHash& qh, Look& k) {
+  const uint32_t l = lane_id();
+  const lsmblk_sst_desc* dp = o.desc + s;
+  const uint32_t blk0 = uni(dp->blk0), nblk = uni(dp->nblk);
+  const uint64_t fo = uni64(o.file_off[s]);
+  const uint8_t* const F = o.files + fo;
+  if (nblk == 0) {  // not opened: the iterator is invalid from the start
+    k.blk = 0;
+    k.ent = 0;
+    return false;
+  }
+  if (filter) {
+    // key_within (lsm_storage.rs:136-138): first_key <= key <= last_key
+    const uint8_t* fk = o.files + uni64(dp->first_key_pos);
+    const uint8_t* lk = o.files + uni64(dp->last_key_pos);
+    uint32_t lcp;
+    if (wave_cmp([&](uint32_t i) { return uint32_t(fk[i]); }, uni(dp->first_key_len), q, lcp) > 0 ||
+        wave_cmp([&](uint32_t i) { return uint32_t(lk[i]); }, uni(dp->last_key_len), q, lcp) < 0) {
+      k.status = LSMBLK_GET_RANGE_OUT;
+      return false;
+    }
+    // Bloom::may_contain (bloom.rs:104-120): probe i tests bit (h + i delta) % (nbits as u32);
+    // the k <= 30 probes are independent: lane i makes probe i, one round trip for all
+    const uint32_t bk = uni(dp->bloom_k);
+    if (bk <= 30) {
+      const uint32_t nbits = uni(dp->bloom_len) * 8u;
+      bool pass = false;
+      if (nbits) {
+        if (!qh.valid) {
+          qh.h = fingerprint32(q, q.len);
+          qh.valid = true;
+        }
+        const uint32_t h = qh.h, delta = (h >> 17) | (h << 15);
+        bool miss = false;
+        if (l < bk) {
+          const uint32_t bit = (h + l * delta) % nbits;
+          miss = !((o.files[uni64(dp->bloom_pos) + (bit >> 3)] >> (bit & 7)) & 1);
+        }
+        pass = __ballot(miss) == 0;
+      }
+      if (!pass) {
+        k.status = LSMBLK_GET_BLOOM_OUT;
+        return false;
+      }
+    }
+  }
+  // find_block_idx (table.rs:253-257): P = partition_point(first_key <= key) (MVCC: < key)
+  const lsmblk_sst_index* const ix = o.index + blk0;
+  const uint32_t P = index_partition(ix, F, nblk, q, mvcc);
+  uint32_t b = P ? P - 1 : 0;
+  bool first = true, bad = false;
+  for (;;) {
+    if (b >= nblk) {  // the iterator ended invalid
+      if (!k.landed) {
+        k.blk = nblk;
+        k.ent = 0;
+      }
+      break;
+    }
+    const uint32_t off = uni(ix[b].off), end = uni(ix[b].end);
+    Visit v{true, true};
+    if (end >= off + 4 + 2 && uint64_t(end) <= uni(dp->meta_offset)) {
+      const uint32_t len = end - off - 4;
+      const uint8_t* src = F + off;
+      const uint32_t lead = uni(uint32_t(reinterpret_cast<uintptr_t>(src) & 15));
+      if (len <= kGetLdsBlock) {
+        // the block and up to 15 bytes on either side (inside the file: `files` is 16-B aligned
+        // and the block's CRC and the sections follow it) in 16-B pieces, all loads first
+        const uint32_t nch = (lead + len + 15) >> 4;
+        u32x4 p[(kGetLdsBlock + 15 + 15) / 1024 + 1];
+        wave_sync();  // the previous block's reads are done
+#pragma unroll
+        for (uint32_t i = 0; i < sizeof(p) / sizeof(p[0]); ++i)
+          if (l + 64 * i < nch) p[i] = *reinterpret_cast<const u32x4*>(src - lead + 16 * (l + 64 * i));
+#pragma unroll
+        for (uint32_t i = 0; i < sizeof(p) / sizeof(p[0]); ++i)
+          if (l + 64 * i < nch) *reinterpret_cast<u32x4*>(S + 16 * (l + 64 * i)) = p[i];
+        wave_sync();
+        v = visit_block(LdsImg{S, lead}, len, fo + off, b, first, mvcc, q, read_ts, k);
+      } else {
+        const rsrc_t R = make_rsrc(reinterpret_cast<const uint8_t*>(uni64(reinterpret_cast<uintptr_t>(src - lead))),
+                                   uni(lead + len));
+        v = visit_block(GlbImg{R, lead}, len, fo + off, b, first, mvcc, q, read_ts, k);
+      }
+    }
+    if (v.bad) {
+      bad = true;
+      k.status = LSMBLK_GET_ABSENT;
+      if (!k.landed) {
+        k.blk = b;
+        k.ent = 0;
+      }
+    }
+    if (v.done) break;
+    ++b;
+    first = false;
+  }
+  return bad;
+}
+
 // 8 waves per SIMD (64 VGPRs): a lookup is a chain of dependent reads, so the lookups in flight hide
 // each other's round trips; the compiler's free choice was 181 VGPRs (2 waves per SIMD).
 __global__ __launch_bounds__(64 * kGetWaves) __attribute__((amdgpu_waves_per_eu(8))) void sst_get_kernel(GetArgs a) {
@@ -553,11 +683,12 @@ __global__ __launch_bounds__(64 * kGetWaves) __attribute__((amdgpu_waves_per_eu(
   const bool mvcc = (a.flags & LSMBLK_GET_MVCC) != 0, filter = !(a.flags & LSMBLK_GET_NO_FILTER);
   const uint32_t qlead = uint32_t(reinterpret_cast<uintptr_t>(a.qkeys) & 3);
   const uint8_t* const qbase = a.qkeys - qlead;
+  const Opened o{a.files, a.file_off, a.desc, a.index};
   uint32_t err = 0, nfound = 0;
   if (blockIdx.x == 0 && threadIdx.x == 0) a.stats[0] = a.nq;
   const uint64_t stride = uint64_t(gridDim.x) * kGetWaves;
   for (uint64_t qi = uint64_t(blockIdx.x) * kGetWaves + wave_id(); qi < a.nq; qi += stride) {
-    Look k{LSMBLK_GET_ABSENT, kNone, kNone, kNone, kNone, 0, 0, 0, false};
+    Look k{LSMBLK_GET_ABSENT, kNone, kNone, kNone, kNone, 0, 0, 0, false, false};
     do {
       const uint32_t s = uni(a.q_sst[qi]);
       const uint32_t k0 = uni(a.qkey_off[qi]), k1 = uni(a.qkey_off[qi + 1]);
@@ -570,98 +701,8 @@ __global__ __launch_bounds__(64 * kGetWaves) __attribute__((amdgpu_waves_per_eu(
         break;
       }
       const QKey q{make_rsrc_exact(const_cast<uint8_t*>(qbase), (qlead + k1 + 3) & ~3u), qlead + k0, k1 - k0};
-      const uint64_t read_ts = uni64(a.q_ts[qi]);
-      const lsmblk_sst_desc* dp = a.desc + s;
-      const uint32_t blk0 = uni(dp->blk0), nblk = uni(dp->nblk);
-      const uint64_t fo = uni64(a.file_off[s]);
-      const uint8_t* const F = a.files + fo;
-      if (nblk == 0) {  // not opened: the iterator is invalid from the start
-        k.blk = 0;
-        k.ent = 0;
-        break;
-      }
-      if (filter) {
-        // key_within (lsm_storage.rs:136-138): first_key <= key <= last_key
-        const uint8_t* fk = a.files + uni64(dp->first_key_pos);
-        const uint8_t* lk = a.files + uni64(dp->last_key_pos);
-        uint32_t lcp;
-        if (wave_cmp([&](uint32_t i) { return uint32_t(fk[i]); }, uni(dp->first_key_len), q, lcp) > 0 ||
-            wave_cmp([&](uint32_t i) { return uint32_t(lk[i]); }, uni(dp->last_key_len), q, lcp) < 0) {
-          k.status = LSMBLK_GET_RANGE_OUT;
-          break;
-        }
-        // Bloom::may_contain (bloom.rs:104-120): probe i tests bit (h + i delta) % (nbits as u32);
-        // the k <= 30 probes are independent: lane i makes probe i, one round trip for all
-        const uint32_t bk = uni(dp->bloom_k);
-        if (bk <= 30) {
-          const uint32_t nbits = uni(dp->bloom_len) * 8u;
-          bool pass = false;
-          if (nbits) {
-            const uint32_t h = fingerprint32(q, q.len), delta = (h >> 17) | (h << 15);
-            bool miss = false;
-            if (l < bk) {
-              const uint32_t bit = (h + l * delta) % nbits;
-              miss = !((a.files[uni64(dp->bloom_pos) + (bit >> 3)] >> (bit & 7)) & 1);
-            }
-            pass = __ballot(miss) == 0;
-          }
-          if (!pass) {
-            k.status = LSMBLK_GET_BLOOM_OUT;
-            break;
-          }
-        }
-      }
-      // find_block_idx (table.rs:253-257): P = partition_point(first_key <= key) (MVCC: < key)
-      const lsmblk_sst_index* const ix = a.index + blk0;
-      const uint32_t P = index_partition(ix, F, nblk, q, mvcc);
-      uint32_t b = P ? P - 1 : 0;
-      bool first = true;
-      for (;;) {
-        if (b >= nblk) {  // the iterator ended invalid
-          if (!k.landed) {
-            k.blk = nblk;
-            k.ent = 0;
-          }
-          break;
-        }
-        const uint32_t off = uni(ix[b].off), end = uni(ix[b].end);
-        Visit v{true, true};
-        if (end >= off + 4 + 2 && uint64_t(end) <= uni(dp->meta_offset)) {
-          const uint32_t len = end - off - 4;
-          const uint8_t* src = F + off;
-          const uint32_t lead = uni(uint32_t(reinterpret_cast<uintptr_t>(src) & 15));
-          if (len <= kGetLdsBlock) {
-            // the block and up to 15 bytes on either side (inside the file: `files` is 16-B aligned
-            // and the block's CRC and the sections follow it) in 16-B pieces, all loads first
-            const uint32_t nch = (lead + len + 15) >> 4;
-            u32x4 p[(kGetLdsBlock + 15 + 15) / 1024 + 1];
-            wave_sync();  // the previous block's reads are done
-#pragma unroll
-            for (uint32_t i = 0; i < sizeof(p) / sizeof(p[0]); ++i)
-              if (l + 64 * i < nch) p[i] = *reinterpret_cast<const u32x4*>(src - lead + 16 * (l + 64 * i));
-#pragma unroll
-            for (uint32_t i = 0; i < sizeof(p) / sizeof(p[0]); ++i)
-              if (l + 64 * i < nch) *reinterpret_cast<u32x4*>(S + 16 * (l + 64 * i)) = p[i];
-            wave_sync();
-            v = visit_block(LdsImg{S, lead}, len, fo + off, b, first, mvcc, q, read_ts, k);
-          } else {
-            const rsrc_t R = make_rsrc(reinterpret_cast<const uint8_t*>(uni64(reinterpret_cast<uintptr_t>(src - lead))),
-                                       uni(lead + len));
-            v = visit_block(GlbImg{R, lead}, len, fo + off, b, first, mvcc, q, read_ts, k);
-          }
-        }
-        if (v.bad) {
-          err |= LSMBLK_ERR_MALFORMED;
-          k.status = LSMBLK_GET_ABSENT;
-          if (!k.landed) {
-            k.blk = b;
-            k.ent = 0;
-          }
-        }
-        if (v.done) break;
-        ++b;
-        first = false;
-      }
+      QHash qh{0, false};
+      if (sst_lookup(o, s, q, uni64(a.q_ts[qi]), mvcc, filter, S, qh, k)) err |= LSMBLK_ERR_MALFORMED;
     } while (false);
     if (k.status == LSMBLK_GET_FOUND) ++nfound;
     if (l == 0) {
@@ -681,10 +722,282 @@ __global__ __launch_bounds__(64 * kGetWaves) __attribute__((amdgpu_waves_per_eu(
   if (nfound && l == 0) atomicAdd(reinterpret_cast<unsigned long long*>(a.stats + 1), (unsigned long long)nfound);
 }
 
+// ---------------------------------------------------------------- the LSM point read
+// lsmblk_lsm_get_batch: the view check, then one wave per key over the view's sources.
+struct LsmGetArgs {
+  const uint8_t* files;
+  const uint64_t* file_off;
+  uint32_t nsst;
+  const lsmblk_sst_desc* desc;
+  const lsmblk_sst_index* index;
+  const uint32_t* l0;
+  uint32_t nl0, nlevel;
+  const uint32_t* level_sst;
+  const uint32_t* level_start;
+  const uint8_t* qkeys;
+  const uint32_t* qkey_off;
+  const uint64_t* q_ts;
+  uint64_t nq;
+  uint32_t flags;
+  lsmblk_lsm_get_result* res;
+  uint8_t* vals;
+  uint64_t val_cap;
+  uint32_t* val_off;
+  uint64_t* stats;
+  uint32_t* vflag;  // the view check's verdict (workspace): error flags, 0 = the lookups run
+};
+
+// key order of file bytes a[0 .. la) against b[0 .. lb) by one lane
+__device__ int lane_cmp2(const uint8_t* x, uint32_t la, const uint8_t* y, uint32_t lb) {
+  const uint32_t mn = la < lb ? la : lb;
+  for (uint32_t i = 0; i < mn; ++i)
+    if (x[i] != y[i]) return x[i] < y[i] ? -1 : 1;
+  return la < lb ? -1 : (la > lb ? 1 : 0);
+}
+
+// The view against the opened set, one lane per view entry (the L0 ids, then the level ids):
+// level_start first, by every workgroup -- it bounds the reads of level_sst -- then per entry the id,
+// its open, and for a level entry with a right neighbour check_sst_valid's order
+// (concat_iterator.rs:82-93), last_key(i) < first_key(i + 1), through the descriptors' key positions.
+__global__ __launch_bounds__(256) void lsm_view_check_kernel(LsmGetArgs a) {
+  int sb = 0;
+  for (uint32_t i = threadIdx.x; i < a.nlevel; i += 256)
+    sb |= (i == 0 && a.level_start[0] != 0) || a.level_start[i + 1] < a.level_start[i];
+  uint32_t err = 0;
+  if (__syncthreads_or(sb)) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) err = LSMBLK_ERR_SEGMENTS;
+  } else {
+    const uint32_t nlv = a.nlevel ? a.level_start[a.nlevel] : 0u;
+    const uint64_t total = uint64_t(a.nl0) + nlv, stride = uint64_t(gridDim.x) * 256;
+    for (uint64_t i = uint64_t(blockIdx.x) * 256 + threadIdx.x; i < total; i += stride) {
+      const bool lv = i >= a.nl0;
+      const uint32_t j = uint32_t(i - a.nl0);  // (a level entry's place in level_sst)
+      const uint32_t t = lv ? a.level_sst[j] : a.l0[i];
+      if (t >= a.nsst) {
+        err |= LSMBLK_ERR_SEGMENTS;
+        continue;
+      }
+      const lsmblk_sst_desc* d = a.desc + t;
+      if (d->err || d->nblk == 0) {
+        err |= LSMBLK_ERR_MALFORMED;
+        continue;
+      }
+      if (!lv || j + 1 >= nlv) continue;
+      // j + 1 starts a level (first l in [1, nlevel] with level_start[l] >= j + 1 equals it): no neighbour
+      uint32_t lo = 1, hi = a.nlevel;
+      while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (a.level_start[mid] >= j + 1) hi = mid;
+        else lo = mid + 1;
+      }
+      if (a.level_start[lo] == j + 1) continue;
+      const uint32_t u = a.level_sst[j + 1];
+      if (u >= a.nsst || a.desc[u].err || a.desc[u].nblk == 0) continue;  // (flagged by its own lane)
+      const lsmblk_sst_desc* e = a.desc + u;
+      if (lane_cmp2(a.files + d->last_key_pos, d->last_key_len, a.files + e->first_key_pos, e->first_key_len) >= 0)
+        err |= LSMBLK_ERR_MALFORMED;
+    }
+  }
+  if (err) {
+    atomicOr(a.vflag, err);
+    atomicOr(reinterpret_cast<unsigned long long*>(a.stats + 3), (unsigned long long)err);
+  }
+}
+
+// A level's source for the query: the tables [0, n) of ls (a level's ids, in key order) with
+// first_key <= q, counted as index_partition counts blocks -- a table's first key is its first
+// block's, so index[desc[t].blk0] holds its image; whole keys only inside the image tie range.
+// Table t's image against the query's: 1 = below it, 2 = not above it.
+__device__ __forceinline__ uint32_t table_img_le(const Opened& o, uint32_t nsst, uint32_t t, uint64_t qhi, uint64_t qlo) {
+  if (t >= nsst) return 0;  // (the view check refuses such a view)
+  const u32x4 v = *reinterpret_cast<const u32x4*>(o.index + o.desc[t].blk0);
+  const uint64_t hi = (uint64_t(v.y) << 32) | v.x, lo = (uint64_t(v.w) << 32) | v.z;
+  return (hi < qhi || (hi == qhi && lo < qlo) ? 1u : 0u) | (hi < qhi || (hi == qhi && lo <= qlo) ? 2u : 0u);
+}
+// ... and the partition point from the image bounds: whole keys inside [iL, iU)
+__device__ __forceinline__ uint32_t level_tie(const Opened& o, uint32_t nsst, const uint32_t* ls, uint32_t iL, uint32_t iU,
+                                              const QKey& q) {
+  if (iU <= iL) return iL;
+  return kary_first_false(iL, iU, [&](uint32_t i) {
+    const uint32_t t = ls[i];
+    if (t >= nsst) return false;
+    return lane_cmp(o.files + o.desc[t].first_key_pos, o.desc[t].first_key_len, q) <= 0;
+  });
+}
+__device__ __forceinline__ uint32_t level_partition(const Opened& o, uint32_t nsst, const uint32_t* ls, uint32_t n,
+                                                    const QKey& q, uint64_t qhi, uint64_t qlo) {
+  const uint32_t iL = kary_first_false(0, n, [&](uint32_t i) { return (table_img_le(o, nsst, ls[i], qhi, qlo) & 1) != 0; });
+  const uint32_t iU = kary_first_false(iL, n, [&](uint32_t i) { return (table_img_le(o, nsst, ls[i], qhi, qlo) & 2) != 0; });
+  return level_tie(o, nsst, ls, iL, iU, q);
+}
+
+// Key order of file bytes p[0 .. len) against the query by one lane: their leading 16 bytes as
+// images (16 independent loads, one round trip) decide unless they tie.
+__device__ __forceinline__ int lane_cmp_img(const uint8_t* p, uint32_t len, const QKey& q, uint64_t qhi, uint64_t qlo) {
+  uint64_t hi = 0, lo = 0;
+#pragma unroll
+  for (uint32_t j = 0; j < 16; ++j) {
+    const uint64_t x = j < len ? p[j] : 0;
+    if (j < 8) hi |= x << (56 - 8 * j);
+    else lo |= x << (56 - 8 * (j - 8));
+  }
+  if (hi != qhi) return hi < qhi ? -1 : 1;
+  if (lo != qlo) return lo < qlo ? -1 : 1;
+  return lane_cmp(p, len, q);
+}
+
+// keep_table (lsm_storage.rs:383-398) by one lane for its own table, in two steps so that the key
+// is hashed only when some table's range holds it: key_within ...
+__device__ __forceinline__ bool lane_key_within(const Opened& o, uint32_t t, const QKey& q, uint64_t qhi, uint64_t qlo) {
+  const lsmblk_sst_desc* d = o.desc + t;
+  if (d->nblk == 0) return false;  // not opened (the view check refuses such a view)
+  return lane_cmp_img(o.files + d->first_key_pos, d->first_key_len, q, qhi, qlo) <= 0 &&
+         lane_cmp_img(o.files + d->last_key_pos, d->last_key_len, q, qhi, qlo) >= 0;
+}
+// ... and Bloom::may_contain (bloom.rs:104-120), every probe made (independent loads)
+__device__ __forceinline__ bool lane_may_contain(const Opened& o, uint32_t t, uint32_t h) {
+  const lsmblk_sst_desc* d = o.desc + t;
+  const uint32_t bk = d->bloom_k, nbits = d->bloom_len * 8u;
+  if (bk > 30) return true;
+  if (!nbits) return false;
+  const uint8_t* B = o.files + d->bloom_pos;
+  const uint32_t delta = (h >> 17) | (h << 15);
+  bool miss = false;
+  for (uint32_t i = 0; i < bk; ++i) {
+    const uint32_t bit = (h + i * delta) % nbits;
+    miss |= !((B[bit >> 3] >> (bit & 7)) & 1);
+  }
+  return !miss;
+}
+
+// One wave per key, grid-strided, over the sources in priority order, 64 at a time:
+//   tables   lane s holds source s's table: an L0 id, or the level's table routed by the wave -- a
+//            view of up to 64 level tables in all has every table's image probed by its own lane
+//            at once and each level's bounds counted out of the two ballots; a larger one runs
+//            level_partition per level
+//   filters  every lane runs keep_table for its own table: the sources' descriptor, key and filter
+//            reads are in flight together, one chain of round trips for all sources instead of one
+//            per source
+//   reads    the sources that passed, in priority order, each by sst_lookup (no filter) through the
+//            wave's LDS image
+// Decider rule: the reads end at the first source whose landing is on the key (or whose path is
+// malformed); bloom_out counts the rejected sources before it.  NEWEST: every passing source is
+// read, the best (ts, lower ordinal) kept.
+__global__ __launch_bounds__(64 * kGetWaves) __attribute__((amdgpu_waves_per_eu(8))) void lsm_get_kernel(LsmGetArgs a) {
+  __shared__ __attribute__((aligned(16))) uint8_t img[kGetWaves][kGetImg];
+  const uint32_t l = lane_id();
+  uint8_t* const S = img[wave_id()];
+  const bool newest = (a.flags & LSMBLK_LSM_GET_NEWEST) != 0, mvcc = newest || (a.flags & LSMBLK_GET_MVCC) != 0;
+  const uint32_t qlead = uint32_t(reinterpret_cast<uintptr_t>(a.qkeys) & 3);
+  const uint8_t* const qbase = a.qkeys - qlead;
+  const Opened o{a.files, a.file_off, a.desc, a.index};
+  const bool run = uni(*a.vflag) == 0;
+  const uint32_t nsrc = a.nl0 + a.nlevel;
+  const uint32_t nlv = run && a.nlevel ? uni(a.level_start[a.nlevel]) : 0u;  // level tables in all
+  uint32_t err = 0, nfound = 0;
+  if (blockIdx.x == 0 && threadIdx.x == 0) a.stats[0] = a.nq;
+  const uint64_t stride = uint64_t(gridDim.x) * kGetWaves;
+  for (uint64_t qi = uint64_t(blockIdx.x) * kGetWaves + wave_id(); qi < a.nq; qi += stride) {
+    // (every per-key state starts here: the answer, the hash and the counters)
+    Look ans{LSMBLK_GET_ABSENT, kNone, kNone, kNone, kNone, 0, 0, 0, false, false};
+    uint32_t asrc = kNone, asst = kNone, seeks = 0, bout = 0;
+    QHash qh{0, false};
+    const uint32_t k0 = uni(a.qkey_off[qi]), k1 = uni(a.qkey_off[qi + 1]);
+    if (run && k1 <= k0) err |= LSMBLK_ERR_EMPTY_KEY;
+    if (run && k1 > k0) {
+      const QKey q{make_rsrc_exact(const_cast<uint8_t*>(qbase), (qlead + k1 + 3) & ~3u), qlead + k0, k1 - k0};
+      const uint64_t read_ts = uni64(a.q_ts[qi]);
+      uint64_t qhi, qlo;
+      query_image(q, qhi, qlo);
+      uint64_t ltm = 0, lem = 0;  // nlv <= 64: level table i's image below / not above the query's
+      if (nlv && nlv <= 64) {
+        const uint32_t c = l < nlv ? table_img_le(o, a.nsst, a.level_sst[l], qhi, qlo) : 0u;
+        ltm = __ballot((c & 1) != 0);
+        lem = __ballot((c & 2) != 0);
+      }
+      bool decided = false;
+      for (uint32_t base = 0; base < nsrc && !decided; base += 64) {
+        const uint32_t cnt = nsrc - base < 64 ? nsrc - base : 64;
+        uint32_t myt = kNone;  // lane s: the table of source base + s
+        if (l < cnt && base + l < a.nl0) myt = a.l0[base + l];
+        for (uint32_t src = base > a.nl0 ? base : a.nl0; src < base + cnt; ++src) {
+          const uint32_t lo = uni(a.level_start[src - a.nl0]), hi = uni(a.level_start[src - a.nl0 + 1]);
+          if (hi <= lo) continue;  // an empty level
+          uint32_t P;
+          if (nlv <= 64) {
+            const uint64_t m = (hi - lo == 64 ? ~0ull : (1ull << (hi - lo)) - 1) << lo;  // hi <= nlv
+            P = level_tie(o, a.nsst, a.level_sst + lo, uint32_t(__builtin_popcountll(ltm & m)),
+                          uint32_t(__builtin_popcountll(lem & m)), q);
+          } else {
+            P = level_partition(o, a.nsst, a.level_sst + lo, hi - lo, q, qhi, qlo);
+          }
+          if (P == 0) continue;    // below the level's first table
+          const uint32_t t = uni(a.level_sst[lo + P - 1]);
+          if (l == src - base) myt = t;
+        }
+        // (a key above the table's last key: a gap of the level, or past it)
+        const bool within = myt < a.nsst && lane_key_within(o, myt, q, qhi, qlo);
+        bool pass = false;
+        if (__ballot(within)) {
+          if (!qh.valid) {
+            qh.h = fingerprint32(q, q.len);
+            qh.valid = true;
+          }
+          pass = within && lane_may_contain(o, myt, qh.h);
+        }
+        uint64_t passm = __ballot(pass), consulted = ~0ull;
+        const uint64_t boutm = __ballot(within && !pass);
+        while (passm) {
+          const uint32_t s = uint32_t(__builtin_ctzll(passm));
+          passm &= passm - 1;
+          const uint32_t t = uint32_t(__builtin_amdgcn_readlane(myt, s));
+          Look k{LSMBLK_GET_ABSENT, kNone, kNone, kNone, kNone, 0, 0, 0, false, false};
+          const bool bad = sst_lookup(o, t, q, read_ts, mvcc, false, S, qh, k);
+          if (bad) err |= LSMBLK_ERR_MALFORMED;
+          ++seeks;
+          if (!newest) {
+            if (k.on_key || bad) {
+              ans = k;
+              asrc = base + s;
+              asst = t;
+              decided = true;
+              consulted = (2ull << s) - 1;  // the sources up to the decider
+              break;
+            }
+          } else if (k.status != LSMBLK_GET_ABSENT && (asrc == kNone || k.ts > ans.ts)) {
+            ans = k;
+            asrc = base + s;
+            asst = t;
+          }
+        }
+        bout += uint32_t(__builtin_popcountll(boutm & consulted));
+      }
+    }
+    if (ans.status == LSMBLK_GET_FOUND) ++nfound;
+    if (l == 0) {
+      lsmblk_lsm_get_result r;
+      r.status = ans.status;
+      r.src = asrc;
+      r.sst = asst;
+      r.hit_blk = ans.hit_blk;
+      r.hit_ent = ans.hit_ent;
+      r.vlen = ans.vlen;
+      r.ts = ans.ts;
+      r.val_pos = ans.val_pos;
+      r.seeks = seeks;
+      r.bloom_out = bout;
+      a.res[qi] = r;
+    }
+  }
+  raise_err(a.stats, err);
+  if (nfound && l == 0) atomicAdd(reinterpret_cast<unsigned long long*>(a.stats + 1), (unsigned long long)nfound);
+}
+
 // val_off = exclusive scan of the FOUND lookups' value sizes: thread t sums the contiguous share
 // [t per, (t + 1) per) of the lookups, the shares are scanned across the workgroup (wave scan, then
 // the wave totals), and every thread writes its share's offsets.
-__global__ __launch_bounds__(1024) void val_scan_kernel(GetArgs a) {
+template <class Args>
+__global__ __launch_bounds__(1024) void val_scan_kernel(Args a) {
   __shared__ uint64_t wsum[16];
   const uint32_t t = threadIdx.x, w = t >> 6;
   const uint64_t per = (a.nq + 1023) / 1024;
@@ -715,7 +1028,8 @@ __global__ __launch_bounds__(1024) void val_scan_kernel(GetArgs a) {
 }
 
 // One wave per lookup, grid-strided: a FOUND lookup's value bytes into its place.
-__global__ __launch_bounds__(256) void val_gather_kernel(GetArgs a) {
+template <class Args>
+__global__ __launch_bounds__(256) void val_gather_kernel(Args a) {
   if (a.stats[3] & (LSMBLK_ERR_CAPACITY | LSMBLK_ERR_OVERFLOW)) return;
   const uint64_t stride = uint64_t(gridDim.x) * 4;
   for (uint64_t q = uint64_t(blockIdx.x) * 4 + wave_id(); q < a.nq; q += stride) {
@@ -1310,9 +1624,48 @@ int lsmblk_sst_get_batch(lsmblk_ctx* c, const uint8_t* files, const uint64_t* fi
   const uint64_t cap = uint64_t(cus > 0 ? cus : 256) * 8, want = (nq + kGetWaves - 1) / kGetWaves;
   LSM_LAUNCH(sst_get_kernel, dim3(uint32_t(want < cap ? want : cap)), dim3(64 * kGetWaves), 0, st, a);
   if (vals) {
-    LSM_LAUNCH(val_scan_kernel, dim3(1), dim3(1024), 0, st, a);
+    LSM_LAUNCH_NAMED("val_scan_kernel", val_scan_kernel<GetArgs>, dim3(1), dim3(1024), 0, st, a);
     const uint64_t gw = (nq + 3) / 4;
-    LSM_LAUNCH(val_gather_kernel, dim3(uint32_t(gw < cap ? gw : cap)), dim3(256), 0, st, a);
+    LSM_LAUNCH_NAMED("val_gather_kernel", val_gather_kernel<GetArgs>, dim3(uint32_t(gw < cap ? gw : cap)), dim3(256), 0, st, a);
+  }
+  return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
+}
+
+int lsmblk_lsm_get_batch(lsmblk_ctx* c, const uint8_t* files, const uint64_t* file_off, uint32_t nsst,
+                         const lsmblk_sst_desc* desc, const lsmblk_sst_index* index, const lsmblk_lsm_view* view,
+                         const uint8_t* qkeys, const uint32_t* qkey_off, const uint64_t* q_ts, uint64_t nq,
+                         uint32_t flags, lsmblk_lsm_get_result* res, uint8_t* vals, uint64_t val_cap, uint32_t* val_off,
+                         uint64_t* stats, void* stream) {
+  if (!c || !stats || !view || (flags & ~(LSMBLK_GET_MVCC | LSMBLK_LSM_GET_NEWEST)) || (vals && !val_off)) return LSMBLK_E_INVAL;
+  if ((view->nl0 && !view->l0) || (view->nlevel && (!view->level_start || !view->level_sst)) ||
+      uint64_t(view->nl0) + view->nlevel >= 0xFFFFFFFFull)
+    return LSMBLK_E_INVAL;
+  if (nq && (!qkey_off || !q_ts || !res || (nsst && (!files || !file_off || !desc)))) return LSMBLK_E_INVAL;
+  if ((reinterpret_cast<uintptr_t>(files) & 15) || (reinterpret_cast<uintptr_t>(index) & 15) || nq >= 0xFFFFFFFFull)
+    return LSMBLK_E_INVAL;
+  std::lock_guard<std::mutex> g(c->mu);
+  DeviceGuard dg(c->device, c);
+  if (!dg.ok) return LSMBLK_E_HIP;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (hipMemsetAsync(stats, 0, LSMBLK_STATS_WORDS * 8, st) != hipSuccess) return LSMBLK_E_HIP;
+  if (nq == 0) {
+    if (vals && hipMemsetAsync(val_off, 0, 4, st) != hipSuccess) return LSMBLK_E_HIP;
+    return LSMBLK_OK;
+  }
+  int rc;
+  if (256 > c->sws_cap && (rc = grow(st, &c->sws, &c->sws_cap, 256, 1))) return rc;
+  if (hipMemsetAsync(c->sws, 0, 256, st) != hipSuccess) return LSMBLK_E_HIP;
+  LsmGetArgs a{files, file_off, nsst, desc, index, view->l0, view->nl0, view->nlevel, view->level_sst, view->level_start,
+               qkeys, qkey_off, q_ts, nq, flags, res, vals, val_cap, val_off, stats, reinterpret_cast<uint32_t*>(c->sws)};
+  int cus = 256;
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
+  const uint64_t cap = uint64_t(cus > 0 ? cus : 256) * 8, want = (nq + kGetWaves - 1) / kGetWaves;
+  LSM_LAUNCH(lsm_view_check_kernel, dim3(32), dim3(256), 0, st, a);
+  LSM_LAUNCH(lsm_get_kernel, dim3(uint32_t(want < cap ? want : cap)), dim3(64 * kGetWaves), 0, st, a);
+  if (vals) {
+    LSM_LAUNCH_NAMED("val_scan_kernel", val_scan_kernel<LsmGetArgs>, dim3(1), dim3(1024), 0, st, a);
+    const uint64_t gw = (nq + 3) / 4;
+    LSM_LAUNCH_NAMED("val_gather_kernel", val_gather_kernel<LsmGetArgs>, dim3(uint32_t(gw < cap ? gw : cap)), dim3(256), 0, st, a);
   }
   return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
 }

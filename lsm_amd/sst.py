@@ -13,7 +13,9 @@
                     (lsmblk_sst_open_batch), answering batches of (sst, key, read_ts) point lookups
                     with the entry and its value (lsmblk_sst_get_batch), and batches of
                     (sst, lower, upper) range scans with every version in range
-                    (lsmblk_sst_scan_batch), filtered to a reader's view by batch.read_filter
+                    (lsmblk_sst_scan_batch), filtered to a reader's view by batch.read_filter; over an
+                    LsmView (L0 tables and levels of the set) batches of keys with one answer per
+                    key, get_with_ts below the memtables (lsmblk_lsm_get_batch)
 
 Device work goes through liblsmblk.so; the footer / section parsing here is host logic that mirrors
 the reference's own (the CRC-32 of those small sections is zlib's, which is crc32fast's).
@@ -26,8 +28,9 @@ import torch
 
 from . import batch
 from ._lib import (LSMBLK_BOUND_EXCLUDED, LSMBLK_BOUND_INCLUDED, LSMBLK_BOUND_UNBOUNDED, LSMBLK_E_CAPACITY,
-                   LSMBLK_GET_FOUND, LSMBLK_GET_MVCC, LSMBLK_GET_NO_FILTER, LSMBLK_SCAN_MVCC, LSMBLK_SCAN_NO_FILTER,
-                   GetResultC, LsmBlkError, ScanResultC, SstDescC, SstIndexC, check, lib)
+                   LSMBLK_GET_FOUND, LSMBLK_GET_MVCC, LSMBLK_GET_NO_FILTER, LSMBLK_LSM_GET_NEWEST, LSMBLK_SCAN_MVCC,
+                   LSMBLK_SCAN_NO_FILTER, GetResultC, LsmBlkError, LsmGetResultC, LsmViewC, ScanResultC, SstDescC,
+                   SstIndexC, check, lib)
 
 
 class MemTable:
@@ -222,12 +225,32 @@ class SsTable:
 
 ERR_CAPACITY = 2  # LSMBLK_ERR_CAPACITY
 GET_FIELDS = ("status", "blk", "ent", "hit_blk", "hit_ent", "vlen", "ts", "val_pos")
+LSM_GET_FIELDS = ("status", "src", "sst", "hit_blk", "hit_ent", "vlen", "ts", "val_pos", "seeks", "bloom_out")
 SCAN_FIELDS = ("status", "blk0", "ent0", "blk1", "ent1", "blocks", "n")
 BOUND_KINDS = {"unbounded": LSMBLK_BOUND_UNBOUNDED, "included": LSMBLK_BOUND_INCLUDED, "excluded": LSMBLK_BOUND_EXCLUDED}
 
 
 def _bound_kind(k):
     return BOUND_KINDS[k] if isinstance(k, str) else int(k)
+
+
+class LsmView:
+    """An LSM view of an SstSet on the device (lsmblk_lsm_view): `l0` the L0 tables' ids in priority
+    order, `levels` per level its ids in key order.  The tables are checked by every lookup call."""
+
+    def __init__(self, l0, levels, device):
+        self.l0 = [int(x) for x in l0]
+        self.levels = [[int(x) for x in lv] for lv in levels]
+        start = np.concatenate([[0], np.cumsum([len(lv) for lv in self.levels])]).astype(np.uint32)
+        flat = [x for lv in self.levels for x in lv]
+        # (never empty tensors: their data pointer is null)
+        self.l0_t = batch._u32_table(np.array(self.l0 or [0], np.uint32), device)
+        self.level_sst_t = batch._u32_table(np.array(flat or [0], np.uint32), device)
+        self.level_start_t = batch._u32_table(start, device)
+
+    def _c(self):
+        return LsmViewC(self.l0_t.data_ptr(), len(self.l0), len(self.levels), self.level_sst_t.data_ptr(),
+                        self.level_start_t.data_ptr())
 
 
 class SstSet:
@@ -390,6 +413,72 @@ class SstSet:
         if st[3]:
             raise LsmBlkError(lib().lsmblk_stats_status(st[3]), "sst get")
         out = {f: r[f].copy() for f in GET_FIELDS}
+        if values:
+            hv = vals[:int(vo[-1])].cpu().numpy() if len(vo) else np.zeros(0, np.uint8)
+            out["val_off"] = vo
+            out["values"] = [hv[vo[i]:vo[i + 1]].tobytes() if r["status"][i] == LSMBLK_GET_FOUND else None
+                             for i in range(len(keys))]
+        return out
+
+    # ---- point reads over an LSM view
+    def view(self, l0, levels):
+        """An LsmView of this set: l0 = SST ids in priority order, levels = per level its ids in key order."""
+        return LsmView(l0, levels, self.device)
+
+    def lsm_get_into(self, view, qkeys, qkey_off, q_ts, nq, flags, res, stats, vals=None, val_cap=0, val_off=None):
+        """Asynchronous lsmblk_lsm_get_batch over device tensors (no host sync): qkey_off int32 (u32),
+        q_ts int64 (u64), res uint8[48 nq], stats int64[4]; vals / val_off None: no gather."""
+        dev = self.device.index
+        batch._need(qkey_off, torch.int32, "qkey_off", dev, nq + 1)
+        batch._need(q_ts, torch.int64, "q_ts", dev, nq)
+        batch._need(res, torch.uint8, "res", dev, nq * ctypes.sizeof(LsmGetResultC))
+        batch._need(stats, torch.int64, "stats", dev, batch.STATS_WORDS)
+        if vals is not None:
+            batch._need(vals, torch.uint8, "vals", dev, val_cap)
+            batch._need(val_off, torch.int32, "val_off", dev, nq + 1)
+        cv = view._c()
+        batch._native("lsmblk_lsm_get_batch", dev, self.stream, batch._ptr(self.files), self.file_off.data_ptr(),
+                      self.nsst, self.desc_t.data_ptr(), batch._ptr(self.index_t), ctypes.byref(cv), qkeys.data_ptr(),
+                      qkey_off.data_ptr(), q_ts.data_ptr(), nq, flags, res.data_ptr(),
+                      vals.data_ptr() if vals is not None else None, val_cap if vals is not None else 0,
+                      val_off.data_ptr() if vals is not None else None, stats.data_ptr(),
+                      batch._stream_ptr(self.stream, dev))
+
+    def lsm_get_raw(self, view, keys, read_ts, flags=0, val_cap=None, vals=None):
+        """One lsmblk_lsm_get_batch call -> (results as a numpy record array, vals tensor or None,
+        val_off numpy or None, stats list); nothing raises on the stats.  val_cap None: no gather."""
+        dev, nq = self.device, len(keys)
+        _, qk, qo, qt = self.upload_queries([0] * nq, keys, read_ts)
+        res = torch.zeros(max(nq, 1) * ctypes.sizeof(LsmGetResultC), dtype=torch.uint8, device=dev)
+        stats = torch.zeros(batch.STATS_WORDS, dtype=torch.int64, device=dev)
+        vo = None
+        if val_cap is not None:
+            if vals is None:
+                vals = batch._aligned_empty(val_cap, dev)
+            vo = torch.zeros(nq + 1, dtype=torch.int32, device=dev)
+        self.lsm_get_into(view, qk, qo, qt, nq, flags, res, stats, vals if val_cap is not None else None, val_cap or 0, vo)
+        torch.cuda.synchronize(dev)
+        r = res.cpu().numpy().view(np.dtype(LsmGetResultC))[:nq]
+        st = [int(x) & 0xFFFFFFFFFFFFFFFF for x in stats.cpu().tolist()]
+        return r, vals, (vo.cpu().numpy().view(np.uint32) if vo is not None else None), st
+
+    def lsm_get(self, view, keys, read_ts, *, mvcc=False, newest=False, values=True):
+        """get_with_ts below the memtables for a batch of keys: key i at read_ts[i] (or the scalar
+        read_ts) over `view` -> dict of numpy arrays (status, src, sst, hit_blk, hit_ent, vlen, ts,
+        val_pos, seeks, bloom_out) and, with `values`, "values" (the FOUND keys' value bytes, None for
+        the others) and "val_off".  mvcc: the corrected landing per table; newest: the version with
+        the largest ts <= read_ts over every source (LSMBLK_LSM_GET_NEWEST)."""
+        flags = (LSMBLK_GET_MVCC if mvcc else 0) | (LSMBLK_LSM_GET_NEWEST if newest else 0)
+        cap = 64 * len(keys) + 1024 if values else None
+        for _ in range(2):
+            r, vals, vo, st = self.lsm_get_raw(view, keys, read_ts, flags, cap)
+            if values and st[3] == ERR_CAPACITY:
+                cap = st[2]
+                continue
+            break
+        if st[3]:
+            raise LsmBlkError(lib().lsmblk_stats_status(st[3]), "lsm get")
+        out = {f: r[f].copy() for f in LSM_GET_FIELDS}
         if values:
             hv = vals[:int(vo[-1])].cpu().numpy() if len(vo) else np.zeros(0, np.uint8)
             out["val_off"] = vo
