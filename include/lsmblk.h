@@ -184,6 +184,12 @@ int lsmblk_ctx_reserve(lsmblk_ctx* ctx, uint64_t max_blocks, uint64_t max_entrie
 #define LSMBLK_DEBUG_SCAN_UNITS 11 /* work units (waves' worth of blocks) lsmblk_sst_scan_batch spreads a batch's
                                       blocks over beyond one per range (default 131072; 0 restores it): with
                                       more blocks than units a unit takes several consecutive blocks */
+#define LSMBLK_DEBUG_EMIT_MODE 12 /* bits 0-7, the emit launch of the encode calls: 0 the default, 1 emit_kernel
+                                     (persistent waves striding over the blocks), 2 emit_block_kernel (one block
+                                     per single-wave workgroup, in dispatch order); same bytes either way (A/B;
+                                     environment LSMBLK_EMIT_MODE at context creation).  Bits 8-31: mode 2's
+                                     grid clamp in workgroups (0: the default), so that a small batch reaches
+                                     the loop over blocks j, j + grid, ... */
 int lsmblk_debug_set(lsmblk_ctx* ctx, int key, uint32_t value);
 /* The trace of the last lagged decode with LSMBLK_DEBUG_COUNTERS on (n <= 16 + 8 * 32768 words;
  * synchronizes).  Words 16 + 8 t + k, 100 MHz s_memrealtime stamps of 64-block tile t: k = 0 tile

@@ -50,6 +50,7 @@ LSMBLK_SCAN_RANGE_OUT = 2
 LSMBLK_SCAN_NO_FILTER = 1
 LSMBLK_SCAN_MVCC = 2
 LSMBLK_DEBUG_SCAN_UNITS = 11
+LSMBLK_DEBUG_EMIT_MODE = 12
 
 
 class LsmBlkError(RuntimeError):

@@ -18,9 +18,13 @@
 //   plan_kernel     one wave per segment: the greedy block-boundary walk (the only serial
 //                   dependency of the format) 64 candidate entries per step with a wave
 //                   prefix sum + ballot; segment totals via the same look-back.
-//   emit_kernel     one wave per output block: keys/values staged into LDS, headers written
-//                   by entry lanes, value bytes moved as aligned dwords, the block image
-//                   flushed with 16-B stores.
+//   emit_kernel     persistent waves, wave w emitting output blocks w, w + nwaves, ... with the
+//                   next block's loads in flight: keys/values staged into LDS, headers written
+//                   by entry lanes, value chunks moved in place with 16-B LDS accesses, the
+//                   block image flushed with 16-B stores.
+//   emit_block_kernel  the same block body in single-wave workgroups, workgroup j emitting blocks
+//                   j, j + grid, ... in dispatch order, nothing prefetched (the default emit
+//                   launch; LSMBLK_DEBUG_EMIT_MODE selects).
 // Blocks or batches that exceed the LDS fast paths take per-entry-lane "simple" paths
 // that read/write global memory directly (same results, slower).
 #include "lsmblk_dev.hpp"
@@ -2033,6 +2037,19 @@ constexpr uint32_t kEmitWaves = 4;
 constexpr uint32_t kEmitKCap = 1088;
 constexpr uint32_t kEmitICap = 4224;  // block image: staged values, then the encoded block (33 swizzle rows)
 constexpr uint32_t kEmitMaxE = 128;
+// The emit launch of the encode calls: 1 = emit_kernel (persistent waves), 2 = emit_block_kernel
+// (single-wave workgroups in dispatch order); LSMBLK_DEBUG_EMIT_MODE / LSMBLK_EMIT_MODE override
+// it.  Measured alternating on one box (profiles/emit_block_ab.json): 2 wins
+// on U, Z and C and ties on M.
+constexpr uint32_t kEmitModeDefault = 2;
+// emit_block_kernel's grid is min(blocks the call can produce, this), workgroup j taking blocks j,
+// j + grid, ...  The block count is known on the device only and a caller's blk_cap can be loose
+// (the compaction passes entries + 2, ~31x its blocks): a workgroup that finds no block costs
+// ~0.17 ns of the launch (C: 1.1 Mi of them 0.19 ms).  And two to four blocks per workgroup
+// measured faster than one (U's 1 Mi blocks: encode stage 1.875 ms at one block each, 1.832 / 1.826
+// at 512 Ki / 256 Ki workgroups, 1.867 at 64 Ki): the workgroup's start -- its LDS, the dependent
+// loads of n and stats -- is paid once.
+constexpr uint64_t kEmitGridMax = 1ull << 18;
 
 struct alignas(16) EmitLds {
   uint8_t kimg[kEmitKCap];
@@ -2041,6 +2058,41 @@ struct alignas(16) EmitLds {
   alignas(16) uint32_t erec[4 * kEmitMaxE];  // per entry: record start | prefix << 16, suffix in kimg | value length << 16, suffix length
   uint64_t ts[kEmitMaxE];
 };
+// emit_block_kernel's LDS: the images and the chunk map only.  What phase 1 leaves per entry for
+// phase 3 (erec, ts) is written and read by the same lane, entry k = 64 it + lane, and lives in
+// registers (EmitRecReg): 6384 B per single-wave workgroup, 25 workgroups per CU by LDS.
+struct alignas(16) EmitBlockLds {
+  uint8_t kimg[kEmitKCap];
+  uint8_t img[kEmitICap];
+  alignas(16) uint32_t cent[kEmitICap / 16 + 4];
+};
+static_assert(sizeof(EmitBlockLds) <= 8192, "at least 20 single-wave workgroups per CU");
+// Where emit_phase1 leaves entry k's record and ts for emit_finish: in the LDS struct (emit_kernel,
+// the fused launch) or in the lane's registers.
+struct EmitRecLds {};
+struct EmitRecReg {
+  uint32_t x[2], y[2], z[2];
+  uint64_t ts[2];
+};
+__device__ __forceinline__ void rec_put_ts(EmitLds& L, EmitRecLds&, uint32_t, uint32_t k, uint64_t v) { L.ts[k] = v; }
+__device__ __forceinline__ void rec_put_ts(EmitBlockLds&, EmitRecReg& R, uint32_t it, uint32_t, uint64_t v) { R.ts[it] = v; }
+__device__ __forceinline__ uint64_t rec_ts(const EmitLds& L, const EmitRecLds&, uint32_t, uint32_t k) { return L.ts[k]; }
+__device__ __forceinline__ uint64_t rec_ts(const EmitBlockLds&, const EmitRecReg& R, uint32_t it, uint32_t) { return R.ts[it]; }
+__device__ __forceinline__ void rec_put(EmitLds& L, EmitRecLds&, uint32_t, uint32_t k, uint32_t x, uint32_t y, uint32_t z) {
+  *reinterpret_cast<u32x4*>(L.erec + 4 * k) = u32x4{x, y, z, 0u};
+}
+__device__ __forceinline__ void rec_put(EmitBlockLds&, EmitRecReg& R, uint32_t it, uint32_t, uint32_t x, uint32_t y, uint32_t z) {
+  R.x[it] = x, R.y[it] = y, R.z[it] = z;
+}
+__device__ __forceinline__ u32x4 rec_get(const EmitLds& L, const EmitRecLds&, uint32_t, uint32_t k) {
+  return *reinterpret_cast<const u32x4*>(L.erec + 4 * k);
+}
+__device__ __forceinline__ u32x4 rec_get(const EmitBlockLds&, const EmitRecReg& R, uint32_t it, uint32_t) {
+  return u32x4{R.x[it], R.y[it], R.z[it], 0u};
+}
+// entry k's record start in the block (the offsets table's value)
+__device__ __forceinline__ uint32_t rec_pos(const EmitLds& L, const EmitRecLds&, uint32_t, uint32_t k) { return L.erec[4 * k] & 0xFFFF; }
+__device__ __forceinline__ uint32_t rec_pos(const EmitBlockLds&, const EmitRecReg& R, uint32_t it, uint32_t) { return R.x[it] & 0xFFFF; }
 
 // bytes [0, len) (len < 16) of v at an unaligned LDS address: overlapping stores of the widest
 // size that fits (8 + 8, 4 + 4, or single bytes)
@@ -2123,8 +2175,8 @@ struct EmitPf {
 // kChk: check every entry against its block's byte ranges (the fused launch, which emits while the
 // plan's helper may still be finding a corrupt stream; emit_kernel runs only after a plan without
 // fatal flags, whose helper has checked every entry's offsets).
-template <bool kChk>
-__device__ __forceinline__ uint32_t emit_phase1(const EmitArgs& a, EmitLds& L, const EmitBlk& B, const EmitPf& pf,
+template <bool kChk, class Lds, class Rec>
+__device__ __forceinline__ uint32_t emit_phase1(const EmitArgs& a, Lds& L, Rec& R, const EmitBlk& B, const EmitPf& pf,
                                                 uint32_t (&eh)[2][4], uint32_t (&et)[2][4], uint32_t& ncs, uint32_t& err) {
   const uint32_t l = lane_id();
   const uint32_t s = B.s, n = B.n, kb0 = B.kb0, vb0 = B.vb0, klead = B.klead, vlead = B.vlead, olead = B.olead, fl = B.fl;
@@ -2148,11 +2200,11 @@ __device__ __forceinline__ uint32_t emit_phase1(const EmitArgs& a, EmitLds& L, c
       uint32_t ko0, ko1, vo0, vo1;
       if (it == 0) {  // prefetched one block ahead
         ko0 = pf.ko0; ko1 = pf.ko1; vo0 = pf.vo0; vo1 = pf.vo1;
-        L.ts[k] = pf.ts;
+        rec_put_ts(L, R, it, k, pf.ts);
       } else {
         ko0 = a.key_off[s + k]; ko1 = a.key_off[s + k + 1];
         vo0 = a.val_off[s + k]; vo1 = a.val_off[s + k + 1];
-        L.ts[k] = a.ts[s + k];
+        rec_put_ts(L, R, it, k, a.ts[s + k]);
       }
       // (kChk) an entry outside its block's byte ranges or of negative length (offsets that
       // decrease: the plan helper refuses such a stream, but the fused launch emits while it
@@ -2196,7 +2248,7 @@ __device__ __forceinline__ uint32_t emit_phase1(const EmitArgs& a, EmitLds& L, c
     dc += __shfl(incl, 63, 64);
     if (k < n) {
       const uint32_t sfx = kl - p;
-      *reinterpret_cast<u32x4*>(L.erec + 4 * k) = u32x4{pos | (p << 16), (klead + kp + p) | (vl << 16), sfx, 0u};
+      rec_put(L, R, it, k, pos | (p << 16), (klead + kp + p) | (vl << 16), sfx);
       // the image chunks lying wholly inside this value -> their source bytes in the staged
       // values (every other chunk keeps ~0)
       {
@@ -2212,8 +2264,8 @@ __device__ __forceinline__ uint32_t emit_phase1(const EmitArgs& a, EmitLds& L, c
 }
 
 // Phases 2b-3 of emit_kernel, the offsets table and the flush of block B's image.
-template <uint32_t EB>
-__device__ __forceinline__ void emit_finish(const EmitArgs& a, EmitLds& L, const EmitBlk& B, uint32_t data_len,
+template <uint32_t EB, class Lds, class Rec>
+__device__ __forceinline__ void emit_finish(const EmitArgs& a, Lds& L, const Rec& R, const EmitBlk& B, uint32_t data_len,
                                             uint32_t ncs, const uint32_t (&eh)[2][4], const uint32_t (&et)[2][4]) {
   const uint32_t l = lane_id();
   const uint32_t n = B.n, olead = B.olead;
@@ -2255,10 +2307,10 @@ __device__ __forceinline__ void emit_finish(const EmitArgs& a, EmitLds& L, const
       const uint32_t k = 64 * it + l;
       if (64 * it >= n) break;
       if (k >= n) continue;
-      const u32x4 er = *reinterpret_cast<const u32x4*>(L.erec + 4 * k);
+      const u32x4 er = rec_get(L, R, it, k);
       const uint32_t pos = er.x & 0xFFFF, p = er.x >> 16, ks = er.y & 0xFFFF, vl = er.y >> 16, sfx = er.z;
       const uint32_t vd = pos + 14 + sfx;
-      const uint64_t tsv = L.ts[k];
+      const uint64_t tsv = rec_ts(L, R, it, k);
       // unaligned LDS stores (the image is not swizzled): every field is one or two stores
       uint8_t* o = L.img;
       const uint32_t ox = olead + pos;
@@ -2286,8 +2338,11 @@ __device__ __forceinline__ void emit_finish(const EmitArgs& a, EmitLds& L, const
   }
   wave_sync();
   // offsets table + entry count (u16 BE, `as u16`)
-  for (uint32_t k = l; k < n; k += 64)
-    *reinterpret_cast<uint16_t*>(L.img + olead + data_len + 2 * k) = uint16_t(bswap16(L.erec[4 * k] & 0xFFFF));
+#pragma unroll
+  for (uint32_t it = 0; it < 2; ++it) {  // (n <= kEmitMaxE: entries l and l + 64)
+    const uint32_t k = 64 * it + l;
+    if (k < n) *reinterpret_cast<uint16_t*>(L.img + olead + data_len + 2 * k) = uint16_t(bswap16(rec_pos(L, R, it, k)));
+  }
   if (l == 0) *reinterpret_cast<uint16_t*>(L.img + olead + data_len + 2 * n) = uint16_t(bswap16(n & 0xFFFF));
   wave_sync();
   // flush the image: 16-B chunks; only the two end chunks can be partial
@@ -2432,7 +2487,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void e
     const EmitBlk B{s, n, O, size, kb0, vb0, klead, vlead, olead, fl, kb1, vb1};
     uint32_t eh[2][4], et[2][4];  // first / last 16 bytes of the value of entries l, l + 64
     uint32_t ncs;
-    const uint32_t data_len = emit_phase1<false>(a, L, B, pf, eh, et, ncs, err);
+    EmitRecLds R;
+    const uint32_t data_len = emit_phase1<false>(a, L, R, B, pf, eh, et, ncs, err);
     // the level-2 loads have landed on every path (on the !has_next path there were none):
     // without this the waitcnt pass keeps them pending past the branch below and waits for
     // the next block's whole prefetch before the chunk moves reuse their registers
@@ -2449,9 +2505,104 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void e
       if (has_next) issue(nxt);
     }
     wave_sync();
-    emit_finish<kEB>(a, L, B, data_len, ncs, eh, et);
+    emit_finish<kEB>(a, L, R, B, data_len, ncs, eh, et);
     if (!has_next) break;
     cur = nxt;
+  }
+  raise_err(a.stats, err);
+}
+
+// Single-wave workgroups in dispatch order: workgroup j emits blocks j, j + grid, ... (one block
+// each up to kEmitGridMax blocks).  Nothing is prefetched across blocks; the overlap comes from the
+// many independent workgroups resident on a CU (95 VGPRs, no scratch, 6384 B of LDS: 20 per CU, 5
+// waves per SIMD, capped by the registers).  Three dependent rounds of loads per block: the block
+// tables (scalar), then the first 64 entries' offsets / ts together with the offsets of the
+// block's end entry (the block's byte bounds: lane 0's entry is its start), then the staging
+// loads.  The body is emit_kernel's (emit_phase1, emit_finish), so are the rules for a block that
+// is not fast or whose table entry is refused.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void emit_block_kernel(EmitArgs a0) {
+  const EmitArgs a = resolve(a0);
+  __shared__ EmitBlockLds L;
+  const uint32_t l = lane_id();
+  const uint64_t nblk = uni64(a.stats[3]) & kPlanFatal ? 0 : uni64(a.stats[0]);
+  const uint64_t lim = nblk < a.blk_cap ? nblk : (a.blk_cap ? a.blk_cap - 1 : 0);  // blk_off[bi+1] must exist
+  if (blockIdx.x >= lim) return;
+  uint32_t err = 0;
+  const uintptr_t kaddr = reinterpret_cast<uintptr_t>(a.keys), vaddr = reinterpret_cast<uintptr_t>(a.vals);
+  cu32_t* const kfirst = kconst(a.blk_first);
+  cu64_t* const koff = kconst(a.blk_off);
+  for (uint64_t bi = blockIdx.x; bi < lim; bi += gridDim.x) {
+    EmitMeta m;  // (as emit_kernel's meta1: a table entry that is not s <= e <= n is refused, none of its entries read)
+    m.bi = bi;
+    m.s = kfirst[bi];
+    m.e = kfirst[bi + 1];
+    m.bad = m.e < m.s || uint64_t(m.e) > a.n;
+    if (m.bad) m.s = m.e = 0;
+    m.n = m.e - m.s;
+    m.O = koff[bi];
+    m.size = a.blk_sz ? uint64_t(kconst(a.blk_sz)[bi]) : koff[bi + 1] - m.O;
+    // a block off the fast path: beyond the LDS image -> flagged for emit_big_kernel; refused -> error
+    auto not_fast = [&] {
+      if (m.bad) err |= LSMBLK_ERR_INTERNAL;
+      else if (l == 0) a.big_flag[bi] = 1;
+    };
+    // (the block tables alone can say so: none of the block's entries is then loaded)
+    if (m.bad || m.n > kEmitMaxE || uint32_t(m.O & 15) + m.size + 8 > kEmitICap) {
+      not_fast();
+      continue;
+    }
+    // round 2: s <= e <= n, so entry s + l < e of the arrays' n + 1 offsets is in bounds, and lane
+    // 0 reads the start bounds of a block without entries too
+    EmitPf pf;
+    const uint32_t r_kb1 = a.key_off[m.e], r_vb1 = a.val_off[m.e];
+    if (l < m.n || l == 0) {
+      pf.ko0 = a.key_off[m.s + l];
+      pf.vo0 = a.val_off[m.s + l];
+    }
+    if (l < m.n) {
+      pf.ko1 = a.key_off[m.s + l + 1];
+      pf.vo1 = a.val_off[m.s + l + 1];
+      pf.ts = a.ts[m.s + l];
+    }
+    m.kb0 = uni(pf.ko0);
+    m.vb0 = uni(pf.vo0);
+    m.kb1 = uni(r_kb1);
+    m.vb1 = uni(r_vb1);
+    const uint32_t klead = uint32_t((kaddr + m.kb0) & 15), vlead = uint32_t((vaddr + m.vb0) & 15);
+    // the staged values and the encoded block share the image (24 B of read slack)
+    if (!(m.kb1 >= m.kb0 && m.vb1 >= m.vb0 && klead + (m.kb1 - m.kb0) + 8 <= kEmitKCap &&
+          vlead + (m.vb1 - m.vb0) + 24 <= kEmitICap)) {
+      not_fast();
+      continue;
+    }
+    // round 3: stage the keys (plain) and values (block image at vlead).  The descriptors end at
+    // the block's bytes, so a lane past them loads nothing; a whole round past them is skipped.
+    const uint32_t nk = (klead + (m.kb1 - m.kb0) + 15) >> 4, nv = (vlead + (m.vb1 - m.vb0) + 15) >> 4;
+    const rsrc_t RK = make_rsrc(a.keys + m.kb0 - klead, klead + (m.kb1 - m.kb0));
+    const rsrc_t RV = make_rsrc(a.vals + m.vb0 - vlead, vlead + (m.vb1 - m.vb0));
+    // (every per-block register array starts defined: left undefined on a skipped round, the
+    // compiler carries the previous block's value around the block loop and spills it)
+    u32x4 kq[2] = {}, vq[5] = {};
+#pragma unroll
+    for (uint32_t i = 0; i < 2; ++i)
+      if (64 * i < nk) kq[i] = __builtin_amdgcn_raw_buffer_load_b128(RK, (l + 64 * i) * 16, 0, kLdAux);
+#pragma unroll
+    for (uint32_t i = 0; i < 5; ++i)
+      if (64 * i < nv) vq[i] = __builtin_amdgcn_raw_buffer_load_b128(RV, (l + 64 * i) * 16, 0, kLdAux);
+#pragma unroll
+    for (uint32_t i = 0; i < 2; ++i)
+      if (l + 64 * i < nk) *reinterpret_cast<u32x4*>(L.kimg + (l + 64 * i) * 16) = kq[i];
+#pragma unroll
+    for (uint32_t i = 0; i < 5; ++i)
+      if (l + 64 * i < nv) *reinterpret_cast<u32x4*>(L.img + (l + 64 * i) * 16) = vq[i];
+    wave_sync();
+    const EmitBlk B{m.s, m.n, m.O, m.size, m.kb0, m.vb0, klead, vlead, uint32_t(m.O & 15), uni(pf.ko1) - m.kb0, m.kb1, m.vb1};
+    uint32_t eh[2][4] = {}, et[2][4] = {};  // first / last 16 bytes of the value of entries l, l + 64
+    uint32_t ncs;
+    EmitRecReg R = {};
+    const uint32_t data_len = emit_phase1<false>(a, L, R, B, pf, eh, et, ncs, err);
+    wave_sync();
+    emit_finish<kEB>(a, L, R, B, data_len, ncs, eh, et);
   }
   raise_err(a.stats, err);
 }
@@ -2917,7 +3068,8 @@ __device__ void fuse_emit(const FuseArgs& f, EmitLds& L) {
     const EmitBlk B{s, n, O, size, kb0, vb0, klead, vlead, olead, fl, kb1, vb1};
     uint32_t eh[2][4], et[2][4];
     uint32_t ncs;
-    const uint32_t data_len = emit_phase1<true>(a, L, B, pf, eh, et, ncs, err);
+    EmitRecLds R;
+    const uint32_t data_len = emit_phase1<true>(a, L, R, B, pf, eh, et, ncs, err);
     __builtin_amdgcn_s_waitcnt(0x0F70);  // s_waitcnt vmcnt(0)
     if (has_next) {
       nxt.kb0 = uni(r_kb0);
@@ -2936,7 +3088,7 @@ __device__ void fuse_emit(const FuseArgs& f, EmitLds& L) {
       }
     }
     wave_sync();
-    emit_finish<1>(a, L, B, data_len, ncs, eh, et);  // (one chunk group: four spill beside the fused launch's walk state)
+    emit_finish<1>(a, L, R, B, data_len, ncs, eh, et);  // (one chunk group: four spill beside the fused launch's walk state)
     if (!has_next) break;
     cur = nxt;
   }
@@ -4067,6 +4219,10 @@ int lsmblk_ctx_create(int device, lsmblk_ctx** out) {
   c->device = device;
   if (const char* e = getenv("LSMBLK_POLL_MODE")) c->poll = uint32_t(atoi(e));
   if (const char* e = getenv("LSMBLK_PLAN_PIPE")) c->plan_pipe = atoi(e) != 0;  // (A/B: LSMBLK_DEBUG_PLAN_PIPE)
+  if (const char* e = getenv("LSMBLK_EMIT_MODE")) {  // (A/B: LSMBLK_DEBUG_EMIT_MODE, the key's value)
+    const unsigned long v = strtoul(e, nullptr, 0);
+    if ((v & 0xFF) <= 2 && v <= 0xFFFFFFFFul) c->emit_mode = uint32_t(v & 0xFF), c->emit_grid = uint32_t(v >> 8);
+  }
   DeviceGuard dg(device);
   if (!dg.ok || hipMalloc(&c->counters, 2048) != hipSuccess) {
     delete c;
@@ -4154,6 +4310,9 @@ int lsmblk_debug_set(lsmblk_ctx* c, int key, uint32_t value) {
     c->fuse_on = value != 0;
   } else if (key == LSMBLK_DEBUG_PLAN_PIPE) {
     c->plan_pipe = value != 0;
+  } else if (key == LSMBLK_DEBUG_EMIT_MODE && (value & 0xFF) <= 2) {
+    c->emit_mode = value & 0xFF;
+    c->emit_grid = value >> 8;
   } else if (key == LSMBLK_DEBUG_SCAN_UNITS && value <= (1u << 24)) {
     c->scan_units = value ? value : kScanUnitsDefault;
   } else if (key == LSMBLK_DEBUG_KERNEL_TIMING) {
@@ -4506,11 +4665,20 @@ int encode_locked(lsmblk_ctx* c, const lsmblk_kv_stream* in, const uint64_t* dn,
     const uint64_t nblk_max = blk_cap < in->n + 1 ? blk_cap : in->n + 1;  // blocks <= entries, <= blk_cap
     if (nblk_max && hipMemsetAsync(c->big_list, 0, nblk_max, st) != hipSuccess) return LSMBLK_E_HIP;
     if (hipGetLastError() != hipSuccess) return LSMBLK_E_HIP;
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, emit_kernel, 256, 0) != hipSuccess || per_cu < 1)
-      per_cu = 3;
-    const uint32_t grid = uint32_t(cus) * uint32_t(per_cu);
-    LSM_LAUNCH_SLOT(4, emit_kernel, dim3(grid), dim3(256), 0, st, e);
+    if ((c->emit_mode ? c->emit_mode : kEmitModeDefault) == 2) {
+      // one single-wave workgroup per block the call can produce; beyond the clamp (a loose
+      // blk_cap: workgroups past the plan's block count only read stats and leave) workgroup j
+      // takes blocks j, j + grid, ...
+      const uint64_t clamp = c->emit_grid ? c->emit_grid : kEmitGridMax;
+      const uint32_t grid = uint32_t(std::max<uint64_t>(1, std::min(nblk_max, clamp)));
+      LSM_LAUNCH_SLOT(4, emit_block_kernel, dim3(grid), dim3(64), 0, st, e);
+    } else {
+      int per_cu = 0;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, emit_kernel, 256, 0) != hipSuccess || per_cu < 1)
+        per_cu = 3;
+      const uint32_t grid = uint32_t(cus) * uint32_t(per_cu);
+      LSM_LAUNCH_SLOT(4, emit_kernel, dim3(grid), dim3(256), 0, st, e);
+    }
   }
   // (every workgroup resident at once: the flagged blocks are strided over the whole grid)
   int big_cu = 0;

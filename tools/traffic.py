@@ -24,7 +24,7 @@ from lsm_amd._build import src_sha  # noqa: E402
 
 # bench.py's roofline keys (its lsmblk_ctx_kernel_times slots) -> the kernels summed into them
 SLOTS = {"decode": ["decode_lag_kernel"], "dec_count": ["dec_count_staged_kernel", "agg_tile_kernel"],
-         "dec_scan": ["dec_scan_kernel"], "plan": ["plan_walk_kernel"], "emit": ["emit_kernel", "emit_big_kernel"],
+         "dec_scan": ["dec_scan_kernel"], "plan": ["plan_walk_kernel"], "emit": ["emit_kernel", "emit_block_kernel", "emit_big_kernel"],
          "decode_two_pass": ["decode_kernel"]}
 
 
