@@ -28,15 +28,16 @@ _NAMES = ("kDecImg", "kDecMaxE", "kDecOut", "kEmitKCap", "kEmitICap", "kEmitMaxE
 
 
 def read_constants(path, names):
-    """{name: value} of `names`, from their `constexpr uint32_t NAME = N;` lines in `path`."""
+    """{name: value} of `names`, from their `constexpr uint32_t NAME = N;` lines in `path` (N a
+    decimal or hexadecimal literal, with or without the `u` suffix)."""
     with open(path) as f:
         text = f.read()
     out = {}
     for name in names:
-        m = re.search(r"^constexpr\s+uint32_t\s+%s\s*=\s*(\d+)\s*;" % name, text, re.M)
+        m = re.search(r"^constexpr\s+uint32_t\s+%s\s*=\s*(0[xX][0-9A-Fa-f]+|\d+)[uU]?\s*;" % name, text, re.M)
         if not m:
             raise RuntimeError(f"{name}: no `constexpr uint32_t {name} = N;` in {path}")
-        out[name] = int(m.group(1))
+        out[name] = int(m.group(1), 0)
     return out
 
 
