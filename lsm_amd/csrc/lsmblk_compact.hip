@@ -231,7 +231,7 @@ __global__ __launch_bounds__(256) void key16_kernel(const uint8_t* keys, const u
   const GKeys G = gkeys(keys, key_off[n]);
   const uint32_t p = key_off[e], kl = key_off[e + 1] - p;
   k16[e] = key16(G, p, kl);
-  if (kl > 0xFFFFu) atomicOr(reinterpret_cast<unsigned long long*>(merr), (unsigned long long)LSMBLK_ERR_SEGMENTS);
+  if (kl > 0xFFFFu) or_word(merr, LSMBLK_ERR_SEGMENTS);
 }
 
 // Every candidate's first 16 key bytes and length, in run-major candidate order (ck, cklen): the
@@ -257,7 +257,7 @@ __global__ __launch_bounds__(256) void cand_rank_kernel(MergeArgs a) {
   const uint32_t c = blockIdx.x * 256 + threadIdx.x;
   if (c == 0) {
     a.mstats[1] = NC;
-    if (!ok) atomicOr(reinterpret_cast<unsigned long long*>(a.mstats + 3), (unsigned long long)LSMBLK_ERR_SEGMENTS);
+    if (!ok) or_err(a.mstats, LSMBLK_ERR_SEGMENTS);
   }
   if (c >= NC) return;
   const GKeys K = gkeys(a.keys, a.key_off[a.n]);
@@ -649,27 +649,17 @@ __global__ __launch_bounds__(256) void tscan_part_kernel(MergeArgs a) {
   if (threadIdx.x == 0) a.tpart[blockIdx.x] = uint64_t(ws[0]) + ws[1] + ws[2] + ws[3];
 }
 
+// (the rounds form of the workgroup scan, lsmblk_dev.hpp)
 __global__ __launch_bounds__(1024) void tscan_top_kernel(MergeArgs a) {
-  const uint32_t t = threadIdx.x, w = t >> 6;
   const uint32_t NC = uint32_t(a.mstats[1]), np = (NC + kTScan - 1) / kTScan;
   __shared__ uint64_t wsum[16];
   uint64_t carry = 0;
-  for (uint32_t r = 0; r < np; r += 1024) {
-    const uint32_t i = r + t;
-    const uint64_t v = i < np ? a.tpart[i] : 0ull;
-    const uint64_t inc = wave_incl_scan<uint64_t>(v);
-    if (lane_id() == 63) wsum[w] = inc;
-    __syncthreads();
-    uint64_t base = carry, tot = carry;
-    for (uint32_t x = 0; x < 16; ++x) {
-      if (x < w) base += wsum[x];
-      tot += wsum[x];
-    }
-    if (i < np) a.tbase[i] = base + inc - v;
-    carry = tot;
-    __syncthreads();
+  for (uint32_t r = 0; r < np; r += kWgScan) {
+    const uint32_t i = r + threadIdx.x;
+    const uint64_t base = block_round1024(i < np ? a.tpart[i] : 0ull, wsum, carry);
+    if (i < np) a.tbase[i] = base;
   }
-  if (t == 0) {
+  if (threadIdx.x == 0) {
     a.tbase[np] = carry;
     a.mstats[0] = carry;
   }
@@ -903,7 +893,7 @@ __global__ __launch_bounds__(256) void mflag_kernel(GatherArgs a) {
         else k = !(a.npfx && prefix_filtered(a, i));        // CompactionFilter::Prefix, :264-275
       }
     } else {
-      atomicOr(reinterpret_cast<unsigned long long*>(a.stats + 3), (unsigned long long)LSMBLK_ERR_MALFORMED);
+      or_err(a.stats, LSMBLK_ERR_MALFORMED);
     }
     a.keep[j] = (k ? 1u : 0u) | same;
     if (k) {
@@ -964,46 +954,24 @@ __global__ __launch_bounds__(256) void mscan_part_kernel(GatherArgs a) {
   }
 }
 
+// (the rounds form of the workgroup scan, lsmblk_dev.hpp; the epilogue's flags start from the merge's)
 __global__ __launch_bounds__(1024) void mscan_top_kernel(GatherArgs a) {
-  const uint32_t t = threadIdx.x, w = t >> 6;
   const uint64_t N = *a.nm, ntiles = (N + kGTile - 1) / kGTile, np = (ntiles + kGScan - 1) / kGScan;
   __shared__ uint64_t wsum[16][3];
   uint64_t carry[3] = {0, 0, 0};
-  for (uint64_t r = 0; r < np; r += 1024) {
-    const uint64_t i = r + t;
-    uint64_t v[3], inc[3];
+  for (uint64_t r = 0; r < np; r += kWgScan) {
+    const uint64_t i = r + threadIdx.x;
+    uint64_t v[3], base[3];
 #pragma unroll
-    for (uint32_t q = 0; q < 3; ++q) {
-      v[q] = i < np ? a.part_sum[3 * i + q] : 0ull;
-      inc[q] = wave_incl_scan<uint64_t>(v[q]);
-      if (lane_id() == 63) wsum[w][q] = inc[q];
-    }
-    __syncthreads();
+    for (uint32_t q = 0; q < 3; ++q) v[q] = i < np ? a.part_sum[3 * i + q] : 0ull;
+    block_round1024<3>(v, wsum, carry, base);
 #pragma unroll
-    for (uint32_t q = 0; q < 3; ++q) {
-      uint64_t base = carry[q], tot = carry[q];
-      for (uint32_t x = 0; x < 16; ++x) {
-        if (x < w) base += wsum[x][q];
-        tot += wsum[x][q];
-      }
-      if (i < np) a.part_pre[3 * i + q] = base + inc[q] - v[q];
-      carry[q] = tot;
-    }
-    __syncthreads();
+    for (uint32_t q = 0; q < 3; ++q)
+      if (i < np) a.part_pre[3 * i + q] = base[q];
   }
-  if (t == 0) {
-    const uint64_t tot[3] = {carry[0], carry[1], carry[2]};
-#pragma unroll
-    for (uint32_t q = 0; q < 3; ++q) a.stats[q] = tot[q];
-    uint32_t err = uint32_t(*a.merr);
-    if (tot[1] > 0xFFFFFFFFull || tot[2] > 0xFFFFFFFFull) err |= LSMBLK_ERR_OVERFLOW;
-    if (tot[0] > a.entry_cap || tot[1] > a.key_cap || tot[2] > a.val_cap) err |= LSMBLK_ERR_CAPACITY;
-    if (!err) {
-      a.okey_off[tot[0]] = uint32_t(tot[1]);
-      a.oval_off[tot[0]] = uint32_t(tot[2]);
-    }
-    if (err) atomicOr(reinterpret_cast<unsigned long long*>(a.stats + 3), (unsigned long long)err);
-  }
+  if (threadIdx.x == 0)
+    publish_totals(a.stats, carry, TotalCaps{a.entry_cap, a.key_cap, a.val_cap}, a.okey_off, a.oval_off, kSentIfClean,
+                   uint32_t(*a.merr));
 }
 
 // Pieces of a lane's 16-B copy loop whose loads are all issued before their stores: a
@@ -1808,8 +1776,7 @@ __global__ __launch_bounds__(256) void shard_seg_kernel(RotArgs a, uint32_t* seg
   const uint64_t N1 = a.n_max + 1;
   if (i == 0) {
     *nseg = uint32_t(segs);
-    if (w[kShSegs] + 1 > seg_cap) atomicOr(reinterpret_cast<unsigned long long*>(a.sstate + kShErr),
-                                           (unsigned long long)LSMBLK_ERR_CAPACITY);
+    if (w[kShSegs] + 1 > seg_cap) or_word(a.sstate + kShErr, LSMBLK_ERR_CAPACITY);
   }
   if (i >= seg_cap) return;
   if (segs == 0) {
@@ -1923,7 +1890,7 @@ __global__ __launch_bounds__(256) void rot_finish_kernel(RotArgs a) {
     if (uint64_t(lo) + 1 > a.sst_cap) err |= LSMBLK_ERR_CAPACITY;  // the chain did not end in the array
     a.stats[0] = lo;
     *a.nsst = err ? 0u : lo;
-    if (err) atomicOr(reinterpret_cast<unsigned long long*>(a.stats + 3), (unsigned long long)err);
+    or_err(a.stats, err);
   }
   __syncthreads();
   for (uint32_t i = s_ns + threadIdx.x; i < a.sst_cap; i += 256) a.starts[i] = uint32_t(n);

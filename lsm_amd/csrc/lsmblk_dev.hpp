@@ -232,8 +232,111 @@ __device__ __forceinline__ uint32_t take_ticket(uint32_t* ctr) {
   return uni(__shfl(t, 0, 64));
 }
 
+// Error flags: or_word ORs err into one 64-bit status word by the calling thread (nothing when
+// err is 0); a call's flags live in stats[3].  or_err is the per-thread entry point, raise_err the
+// wave-wide one (every lane calls it with the wave's flags, lane 0 acts).
+__device__ __forceinline__ void or_word(uint64_t* word, uint32_t err) {
+  if (err) atomicOr(reinterpret_cast<unsigned long long*>(word), (unsigned long long)err);
+}
+__device__ __forceinline__ void or_err(uint64_t* stats, uint32_t err) { or_word(stats + 3, err); }
 __device__ __forceinline__ void raise_err(uint64_t* stats, uint32_t err) {
-  if (err && lane_id() == 0) atomicOr(reinterpret_cast<unsigned long long*>(stats + 3), (unsigned long long)err);
+  if (lane_id() == 0) or_err(stats, err);
+}
+
+// ---------------------------------------------------------------- one-workgroup scan
+// The top-level scan of every batched call: one workgroup of kWgScan threads (16 waves) over n
+// items, in one of two forms.
+//   share form   thread t sums its contiguous share of the items (share1024), the 1024 sums are
+//                scanned once (block_excl1024) and the thread walks its share again from its base:
+//                for items whose values are re-read or recomputed, any n in two barriers.
+//   rounds form  rounds of 1024 consecutive items, thread t item r + t (coalesced loads), each
+//                round's scan on top of a carry (block_round1024): for items loaded once.
+constexpr uint32_t kWgScan = 1024;
+
+// thread t's contiguous share [x0, x1) of n items
+__device__ __forceinline__ void share1024(uint64_t n, uint64_t& x0, uint64_t& x1) {
+  const uint64_t per = (n + kWgScan - 1) / kWgScan, t = threadIdx.x;
+  x0 = per * t < n ? per * t : n;
+  x1 = x0 + per < n ? x0 + per : n;
+}
+// Exclusive prefixes of the NQ sums v over the workgroup's 1024 threads, and the totals (in every
+// thread).  wsum: 16 x NQ words of LDS, free again after the call's second barrier.
+template <int NQ>
+__device__ __forceinline__ void block_excl1024(const uint64_t (&v)[NQ], uint64_t (*wsum)[NQ], uint64_t (&base)[NQ],
+                                               uint64_t (&tot)[NQ]) {
+  static_assert(kWgScan == 16 * 64, "16 wave sums");
+  const uint32_t w = threadIdx.x >> 6;
+  uint64_t inc[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) inc[q] = wave_incl_scan<uint64_t>(v[q]);
+  // (pinned after the wave scans: the compiler otherwise moves the barrier above them, so that
+  // every round waits for its slowest wave before any wave scans: sst_layout_kernel 7.6 -> 8.4 us
+  // at 2500 SSTs, profiles/top_scan_ab.json)
+  __builtin_amdgcn_sched_barrier(0);
+  __syncthreads();  // wsum's previous use is over
+  if (lane_id() == 63) {
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) wsum[w][q] = inc[q];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    uint64_t b = 0, s = 0;
+    for (uint32_t x = 0; x < 16; ++x) {
+      if (x < w) b += wsum[x][q];
+      s += wsum[x][q];
+    }
+    base[q] = b + inc[q] - v[q];
+    tot[q] = s;
+  }
+}
+__device__ __forceinline__ uint64_t block_excl1024(uint64_t v, uint64_t* wsum, uint64_t& tot) {
+  const uint64_t v1[1] = {v};
+  uint64_t b[1], s[1];
+  block_excl1024<1>(v1, reinterpret_cast<uint64_t(*)[1]>(wsum), b, s);
+  tot = s[0];
+  return b[0];
+}
+// One round of the rounds form: base = carry + the round's exclusive prefixes, carry += its totals.
+template <int NQ>
+__device__ __forceinline__ void block_round1024(const uint64_t (&v)[NQ], uint64_t (*wsum)[NQ], uint64_t (&carry)[NQ],
+                                                uint64_t (&base)[NQ]) {
+  uint64_t tot[NQ];
+  block_excl1024<NQ>(v, wsum, base, tot);
+#pragma unroll
+  for (int q = 0; q < NQ; ++q) {
+    base[q] += carry[q];
+    carry[q] += tot[q];
+  }
+}
+__device__ __forceinline__ uint64_t block_round1024(uint64_t v, uint64_t* wsum, uint64_t& carry) {
+  uint64_t tot;
+  const uint64_t base = carry + block_excl1024(v, wsum, tot);
+  carry += tot;
+  return base;
+}
+
+// The totals epilogue of a batched call, by exactly one thread: stats[0..2] = tot (entries, key
+// bytes, value bytes), LSMBLK_ERR_OVERFLOW when the key or value bytes (with ovf_entries, the
+// entries too) pass 2^32, LSMBLK_ERR_CAPACITY when a total passes its cap, the key_off[N] /
+// val_off[N] sentinels, and err (seeded by the caller) ORed into stats[3].  The sentinels go out
+// when the call is clean (kSentIfClean) or whenever N fits (kSentIfFits); never through null
+// pointers (a call without outputs, which passes caps of ~0 as well).
+enum SentinelRule { kSentIfClean, kSentIfFits };
+struct TotalCaps {
+  uint64_t entry, key, val;
+};
+__device__ __forceinline__ void publish_totals(uint64_t* stats, const uint64_t (&tot)[3], const TotalCaps& cap,
+                                               uint32_t* okey_off, uint32_t* oval_off, SentinelRule rule,
+                                               uint32_t err = 0, bool ovf_entries = false) {
+  for (uint32_t q = 0; q < 3; ++q) stats[q] = tot[q];
+  if ((ovf_entries && tot[0] > 0xFFFFFFFFull) || tot[1] > 0xFFFFFFFFull || tot[2] > 0xFFFFFFFFull) err |= LSMBLK_ERR_OVERFLOW;
+  if (tot[0] > cap.entry || tot[1] > cap.key || tot[2] > cap.val) err |= LSMBLK_ERR_CAPACITY;
+  if (okey_off && (rule == kSentIfFits ? tot[0] <= cap.entry : !err)) {
+    okey_off[tot[0]] = uint32_t(tot[1]);
+    oval_off[tot[0]] = uint32_t(tot[2]);
+  }
+  or_err(stats, err);
 }
 
 // len bytes src -> dst by the whole wave, any alignment (16-B pieces, 1 KiB per instruction).

@@ -69,13 +69,13 @@ struct OpenArgs {
 // decreases (the next entry belongs to the file before), which the CRC pass skips.  A failed SST's
 // four entries are its file's start: empty ranges.
 __global__ __launch_bounds__(1024) void sst_open_prep_kernel(OpenArgs a) {
-  const uint32_t t = threadIdx.x, w = t >> 6;
+  const uint32_t t = threadIdx.x;
   __shared__ uint64_t wsum[16];
   int tb = 0;
-  for (uint32_t s = t; s < a.nsst; s += 1024) tb |= a.file_off[s + 1] < a.file_off[s];
+  for (uint32_t s = t; s < a.nsst; s += kWgScan) tb |= a.file_off[s + 1] < a.file_off[s];
   const bool tbad = __syncthreads_or(tb) != 0;
   uint64_t carry = 0;
-  for (uint32_t r = 0; r < a.nsst; r += 1024) {
+  for (uint32_t r = 0; r < a.nsst; r += kWgScan) {  // the rounds form of the workgroup scan
     const uint32_t s = r + t;
     uint64_t cnt = 0;
     if (s < a.nsst) {
@@ -116,24 +116,15 @@ __global__ __launch_bounds__(1024) void sst_open_prep_kernel(OpenArgs a) {
       e[3] = ok ? fo + flen - 8 : fo;
       if (s == 0) a.tab[4ull * a.nsst] = e[3];  // an empty last range
     }
-    const uint64_t inc = wave_incl_scan<uint64_t>(cnt);
-    if (lane_id() == 63) wsum[w] = inc;
-    __syncthreads();
-    uint64_t base = carry, tot = carry;
-    for (uint32_t x = 0; x < 16; ++x) {
-      if (x < w) base += wsum[x];
-      tot += wsum[x];
-    }
-    if (s < a.nsst) a.desc[s].blk0 = uint32_t(base + inc - cnt);
-    carry = tot;
-    __syncthreads();
+    const uint64_t base = block_round1024(cnt, wsum, carry);
+    if (s < a.nsst) a.desc[s].blk0 = uint32_t(base);
   }
   if (t == 0) {
     uint32_t e = tbad ? LSMBLK_ERR_MALFORMED : 0u;
     a.stats[1] = carry;
     if (carry > 0xFFFFFFFFull) e |= LSMBLK_ERR_OVERFLOW;
     if (carry > a.index_cap) e |= LSMBLK_ERR_CAPACITY;
-    if (e) atomicOr(reinterpret_cast<unsigned long long*>(a.stats + 3), (unsigned long long)e);
+    or_err(a.stats, e);
   }
 }
 
@@ -146,7 +137,7 @@ __global__ __launch_bounds__(64) void sst_open_walk_kernel(OpenArgs a) {
   const uint32_t s = blockIdx.x, l = threadIdx.x;
   lsmblk_sst_desc d = a.desc[s];
   if (d.err) {
-    if (l == 0) atomicOr(reinterpret_cast<unsigned long long*>(a.stats + 2), (unsigned long long)d.err);
+    if (l == 0) or_word(a.stats + 2, d.err);
     return;
   }
   const uint64_t fo = a.file_off[s], fend = a.file_off[s + 1];
@@ -256,7 +247,7 @@ __global__ __launch_bounds__(64) void sst_open_walk_kernel(OpenArgs a) {
       d.max_ts = mt;
       atomicAdd(reinterpret_cast<unsigned long long*>(a.stats), 1ull);
     } else {
-      atomicOr(reinterpret_cast<unsigned long long*>(a.stats + 2), (unsigned long long)err);
+      or_word(a.stats + 2, err);
     }
     d.err = err;
     a.desc[s] = d;
@@ -800,7 +791,7 @@ __global__ __launch_bounds__(256) void lsm_view_check_kernel(LsmGetArgs a) {
   }
   if (err) {
     atomicOr(a.vflag, err);
-    atomicOr(reinterpret_cast<unsigned long long*>(a.stats + 3), (unsigned long long)err);
+    or_err(a.stats, err);
   }
 }
 
@@ -993,37 +984,29 @@ __global__ __launch_bounds__(64 * kGetWaves) __attribute__((amdgpu_waves_per_eu(
   if (nfound && l == 0) atomicAdd(reinterpret_cast<unsigned long long*>(a.stats + 1), (unsigned long long)nfound);
 }
 
-// val_off = exclusive scan of the FOUND lookups' value sizes: thread t sums the contiguous share
-// [t per, (t + 1) per) of the lookups, the shares are scanned across the workgroup (wave scan, then
-// the wave totals), and every thread writes its share's offsets.
+// val_off = exclusive scan of the FOUND lookups' value sizes: the share form of the workgroup
+// scan (lsmblk_dev.hpp) over the lookups.
 template <class Args>
 __global__ __launch_bounds__(1024) void val_scan_kernel(Args a) {
   __shared__ uint64_t wsum[16];
-  const uint32_t t = threadIdx.x, w = t >> 6;
-  const uint64_t per = (a.nq + 1023) / 1024;
-  const uint64_t q0 = per * t < a.nq ? per * t : a.nq, q1 = q0 + per < a.nq ? q0 + per : a.nq;
-  uint64_t sum = 0;
+  uint64_t q0, q1;
+  share1024(a.nq, q0, q1);
+  uint64_t sum = 0, tot;
   for (uint64_t q = q0; q < q1; ++q) sum += a.res[q].status == LSMBLK_GET_FOUND ? a.res[q].vlen : 0u;
-  const uint64_t inc = wave_incl_scan<uint64_t>(sum);
-  if (lane_id() == 63) wsum[w] = inc;
-  __syncthreads();
-  uint64_t base = 0, tot = 0;
-  for (uint32_t x = 0; x < 16; ++x) {
-    if (x < w) base += wsum[x];
-    tot += wsum[x];
-  }
-  uint64_t o = base + inc - sum;
+  uint64_t o = block_excl1024(sum, wsum, tot);
   for (uint64_t q = q0; q < q1; ++q) {
     a.val_off[q] = uint32_t(o);
     o += a.res[q].status == LSMBLK_GET_FOUND ? a.res[q].vlen : 0u;
   }
-  if (t == 0) {
+  // (not publish_totals: one total, in stats[2], and val_off has one entry per lookup, found or
+  // not, so its sentinel index is nq whatever the total)
+  if (threadIdx.x == 0) {
     a.val_off[a.nq] = uint32_t(tot);
     a.stats[2] = tot;
     uint32_t e = 0;
     if (tot > 0xFFFFFFFFull) e |= LSMBLK_ERR_OVERFLOW;
     if (tot > a.val_cap) e |= LSMBLK_ERR_CAPACITY;
-    if (e) atomicOr(reinterpret_cast<unsigned long long*>(a.stats + 3), (unsigned long long)e);
+    or_err(a.stats, e);
   }
 }
 
@@ -1293,28 +1276,7 @@ __global__ __launch_bounds__(64 * kGetWaves) void scan_bounds_kernel(ScanArgs a)
   raise_err(a.stats, err);
 }
 
-// thread t's contiguous share [x0, x1) of n items over the kScanWg threads of a workgroup
-__device__ __forceinline__ void share1024(uint64_t n, uint64_t& x0, uint64_t& x1) {
-  const uint64_t per = (n + kScanWg - 1) / kScanWg, t = threadIdx.x;
-  x0 = per * t < n ? per * t : n;
-  x1 = x0 + per < n ? x0 + per : n;
-}
-// exclusive prefix of v over the workgroup's 1024 threads, and the total
-__device__ __forceinline__ uint64_t block_excl1024(uint64_t v, uint64_t* wsum, uint64_t& tot) {
-  static_assert(kScanWg == 1024, "16 wave sums");
-  const uint32_t w = threadIdx.x >> 6;
-  const uint64_t inc = wave_incl_scan<uint64_t>(v);
-  __syncthreads();  // wsum's previous use is over
-  if (lane_id() == 63) wsum[w] = inc;
-  __syncthreads();
-  uint64_t base = 0;
-  tot = 0;
-  for (uint32_t x = 0; x < 16; ++x) {
-    if (x < w) base += wsum[x];
-    tot += wsum[x];
-  }
-  return base + inc - v;
-}
+static_assert(kScanWg == kWgScan, "share1024 / block_excl1024 (lsmblk_dev.hpp) serve a workgroup of kWgScan threads");
 
 __global__ __launch_bounds__(kScanWg) void scan_units_kernel(ScanArgs a) {
   __shared__ uint64_t wsum[16];
@@ -1412,7 +1374,7 @@ __global__ __launch_bounds__(64 * kGetWaves) void scan_count_kernel(ScanArgs a) 
 }
 
 __global__ __launch_bounds__(kScanWg) void scan_offsets_kernel(ScanArgs a) {
-  __shared__ uint64_t wsum[16];
+  __shared__ uint64_t wsum[16][3];
   const uint64_t nu = a.hdr[0];
   uint64_t u0, u1;
   share1024(nu, u0, u1);
@@ -1441,7 +1403,7 @@ __global__ __launch_bounds__(kScanWg) void scan_offsets_kernel(ScanArgs a) {
     for (uint64_t u = u0; u < u1; ++u)
       for (uint32_t k = 0; k < 3; ++k) sum[k] += a.ucnt[3 * u + k];
   }
-  for (uint32_t k = 0; k < 3; ++k) base[k] = block_excl1024(sum[k], wsum, tot[k]);
+  block_excl1024<3>(sum, wsum, base, tot);
   if (!masked) {
     for (uint64_t u = u0; u < u1; ++u)
       for (uint32_t k = 0; k < 3; ++k) {
@@ -1462,17 +1424,11 @@ __global__ __launch_bounds__(kScanWg) void scan_offsets_kernel(ScanArgs a) {
     }
   }
   if (threadIdx.x == 0) {
-    uint32_t e = 0;
-    for (uint32_t k = 0; k < 3; ++k) {
-      a.stats[k] = tot[k];
-      if (tot[k] > 0xFFFFFFFFull) e |= LSMBLK_ERR_OVERFLOW;
-    }
-    if (a.has_out && (tot[0] > a.entry_cap || tot[1] > a.key_cap || tot[2] > a.val_cap)) e |= LSMBLK_ERR_CAPACITY;
-    if (a.has_out && !e) {
-      a.okey_off[tot[0]] = uint32_t(tot[1]);
-      a.oval_off[tot[0]] = uint32_t(tot[2]);
-    }
-    if (e) atomicOr(reinterpret_cast<unsigned long long*>(a.stats + 3), (unsigned long long)e);
+    // the entry total is held to 2^32 as well (seg_start holds u32 positions in it); a counting
+    // call (no outputs) has no caps and no sentinels
+    const TotalCaps caps = a.has_out ? TotalCaps{a.entry_cap, a.key_cap, a.val_cap} : TotalCaps{~0ull, ~0ull, ~0ull};
+    publish_totals(a.stats, tot, caps, a.has_out ? a.okey_off : nullptr, a.has_out ? a.oval_off : nullptr, kSentIfClean, 0,
+                   /*ovf_entries=*/true);
   }
   __threadfence_block();
   __syncthreads();  // the unit prefixes are written

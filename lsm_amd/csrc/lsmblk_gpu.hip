@@ -1284,8 +1284,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8))) void de
 }
 
 // ---------------------------------------------------------------- decode pass 2: tile scan
-// One workgroup: exclusive scan of the per-tile sums; totals, capacity / overflow checks and
-// the key_off[N] / val_off[N] sentinels.
+// One workgroup: exclusive scan of the per-tile sums (the share form of the workgroup scan,
+// lsmblk_dev.hpp), then the totals epilogue (publish_totals).
 struct ScanArgs {
   const uint64_t* tile_sum;
   uint64_t* tile_pre;
@@ -1299,62 +1299,29 @@ struct ScanArgs {
 };
 
 __global__ __launch_bounds__(1024) void dec_scan_kernel(ScanArgs a) {
-  __shared__ uint64_t part[32][3];  // wave totals, then wave bases
-  const uint32_t t = threadIdx.x;
-  const uint64_t per = (a.ntiles + 1023) / 1024, lo = t * per, hi = lo + per < a.ntiles ? lo + per : a.ntiles;
-  uint64_t s0 = 0, s1 = 0, s2 = 0;
+  __shared__ uint64_t wsum[16][3];
+  uint64_t lo, hi;
+  share1024(a.ntiles, lo, hi);
+  uint64_t s[3] = {0, 0, 0}, e[3], tot[3];
 #pragma unroll 8
   for (uint64_t i = lo; i < hi; ++i) {  // (unrolled: the tiles' loads in flight together)
-    s0 += a.tile_sum[3 * i];
-    s1 += a.tile_sum[3 * i + 1];
-    s2 += a.tile_sum[3 * i + 2];
+#pragma unroll
+    for (uint32_t q = 0; q < 3; ++q) s[q] += a.tile_sum[3 * i + q];
   }
-  // block scan of the 1024 partials: wave scans, then one wave over the 16 wave totals (two
-  // barriers; a Hillis-Steele scan over LDS took twenty)
-  const uint32_t l = t & 63, w = t >> 6;
-  uint64_t i0 = wave_incl_scan<uint64_t>(s0), i1 = wave_incl_scan<uint64_t>(s1), i2 = wave_incl_scan<uint64_t>(s2);
-  if (l == 63) {
-    part[w][0] = i0;
-    part[w][1] = i1;
-    part[w][2] = i2;
-  }
-  __syncthreads();
-  if (w == 0) {
-    uint64_t x0 = l < 16 ? part[l][0] : 0, x1 = l < 16 ? part[l][1] : 0, x2 = l < 16 ? part[l][2] : 0;
-    const uint64_t y0 = wave_incl_scan<uint64_t>(x0), y1 = wave_incl_scan<uint64_t>(x1), y2 = wave_incl_scan<uint64_t>(x2);
-    if (l < 16) {
-      part[16 + l][0] = y0 - x0;  // exclusive wave bases
-      part[16 + l][1] = y1 - x1;
-      part[16 + l][2] = y2 - x2;
-    }
-  }
-  __syncthreads();
-  i0 += part[16 + w][0];
-  i1 += part[16 + w][1];
-  i2 += part[16 + w][2];
-  uint64_t e0 = i0 - s0, e1 = i1 - s1, e2 = i2 - s2;
+  block_excl1024<3>(s, wsum, e, tot);
+  // (the three stores, then the three loads, two instructions each: tile_pre may alias tile_sum, so
+  // one loop over the sums stays store, load, store, load, ... -- 74 against 53 us at 16384 tiles)
   for (uint64_t i = lo; i < hi; ++i) {
-    a.tile_pre[3 * i] = e0;
-    a.tile_pre[3 * i + 1] = e1;
-    a.tile_pre[3 * i + 2] = e2;
-    e0 += a.tile_sum[3 * i];
-    e1 += a.tile_sum[3 * i + 1];
-    e2 += a.tile_sum[3 * i + 2];
+#pragma unroll
+    for (uint32_t q = 0; q < 3; ++q) a.tile_pre[3 * i + q] = e[q];
+#pragma unroll
+    for (uint32_t q = 0; q < 3; ++q) e[q] += a.tile_sum[3 * i + q];
   }
-  if (t == 1023) {
-    const uint64_t N = i0, K = i1, V = i2;
-    if (a.blk_ent) a.blk_ent[a.nblk] = N;
-    a.stats[0] = N;
-    a.stats[1] = K;
-    a.stats[2] = V;
-    uint32_t err = 0;
-    if (K > 0xFFFFFFFFull || V > 0xFFFFFFFFull) err |= LSMBLK_ERR_OVERFLOW;
-    if (N > a.entry_cap || K > a.key_cap || V > a.val_cap) err |= LSMBLK_ERR_CAPACITY;
-    if (N <= a.entry_cap) {
-      a.key_off[N] = uint32_t(K);
-      a.val_off[N] = uint32_t(V);
-    }
-    if (err) atomicOr(reinterpret_cast<unsigned long long*>(a.stats + 3), (unsigned long long)err);
+  if (threadIdx.x == 0) {
+    if (a.blk_ent) a.blk_ent[a.nblk] = tot[0];
+    // kSentIfFits: the decode writes its sentinels whenever the entry count fits, whatever else
+    // is raised (the other calls only when clean)
+    publish_totals(a.stats, tot, TotalCaps{a.entry_cap, a.key_cap, a.val_cap}, a.key_off, a.val_off, kSentIfFits);
   }
 }
 
@@ -3157,7 +3124,7 @@ __global__ __launch_bounds__(256) void slot_tables_kernel(FuseArgs f, uint32_t* 
       f.p.stats[0] = nblk;
       if (nblk + 1 > blk_cap) err |= LSMBLK_ERR_CAPACITY;
     }
-    if (err) atomicOr(reinterpret_cast<unsigned long long*>(f.p.stats + 3), (unsigned long long)err);
+    or_err(f.p.stats, err);
   }
 }
 
@@ -3613,10 +3580,6 @@ struct MetaBlk {
   bool ok;
 };
 
-__device__ __forceinline__ void or_err(uint64_t* stats, uint32_t err) {
-  if (err) atomicOr(reinterpret_cast<unsigned long long*>(stats + 3), (unsigned long long)err);
-}
-
 // Parse block b's first key length and last entry; ok = false where the reference would panic
 // (no entries, trailer/offsets past the block, first or last entry past the data).
 __device__ MetaBlk meta_parse(const MetaArgs& a, uint64_t b) {
@@ -3658,29 +3621,24 @@ __global__ __launch_bounds__(256) void meta_size_kernel(MetaArgs a) {
   if (threadIdx.x == 0) a.tile_sum[blockIdx.x] = uint64_t(ws[0]) + ws[1] + ws[2] + ws[3];
 }
 
-// One workgroup: exclusive scan of the tile sums, the total, the capacity check and the
-// segment-table check (seg_blk[0] = 0, non-decreasing, seg_blk[nseg] = nblk).
+// One workgroup: exclusive scan of the tile sums (the share form of the workgroup scan,
+// lsmblk_dev.hpp), the total, the capacity check and the segment-table check (seg_blk[0] = 0,
+// non-decreasing, seg_blk[nseg] = nblk).
 __global__ __launch_bounds__(1024) void meta_scan_kernel(MetaArgs a) {
   const uint32_t t = threadIdx.x;
-  const uint64_t ntiles = (a.nblk + kMetaTile - 1) / kMetaTile;
-  const uint64_t per = (ntiles + 1023) / 1024;
-  const uint64_t lo = min(ntiles, t * per), hi = min(ntiles, lo + per);
-  uint64_t s = 0;
-  for (uint64_t i = lo; i < hi; ++i) s += a.tile_sum[i];
   __shared__ uint64_t wsum[16];
-  const uint64_t inc = wave_incl_scan<uint64_t>(s);
-  if (lane_id() == 63) wsum[t >> 6] = inc;
-  __syncthreads();
-  uint64_t base = 0;
-  for (uint32_t w = 0; w < (t >> 6); ++w) base += wsum[w];
-  uint64_t run = base + inc - s;
+  uint64_t lo, hi;
+  share1024((a.nblk + kMetaTile - 1) / kMetaTile, lo, hi);
+  uint64_t s = 0, total;
+  for (uint64_t i = lo; i < hi; ++i) s += a.tile_sum[i];
+  uint64_t run = block_excl1024(s, wsum, total);
   for (uint64_t i = lo; i < hi; ++i) {
     a.tile_pre[i] = run;
     run += a.tile_sum[i];
   }
   uint32_t err = 0;
   if (t == 1023) {
-    const uint64_t total = base + inc, need = total + 16ull * a.nseg;
+    const uint64_t need = total + 16ull * a.nseg;
     a.pos[a.nblk] = total;
     a.stats[0] = a.nseg;
     a.stats[1] = need;
@@ -3937,60 +3895,23 @@ __global__ __launch_bounds__(256) void filt_flag_kernel(FiltArgs a) {
   }
 }
 
-// Rounds of 1024 consecutive tiles (coalesced loads), each a workgroup scan plus the carry.
+// The rounds form of the workgroup scan (lsmblk_dev.hpp) over the tiles, then the totals epilogue.
 __global__ __launch_bounds__(1024) void filt_scan_kernel(FiltArgs a) {
-  const uint32_t t = threadIdx.x, w = t >> 6;
   const uint64_t ntiles = (a.n + kFiltTile - 1) / kFiltTile;
   __shared__ uint64_t wsum[16][3];
   uint64_t carry[3] = {0, 0, 0};
-  for (uint64_t r = 0; r < ntiles; r += 1024) {
-    const uint64_t i = r + t;
-    uint64_t v[3], inc[3];
+  for (uint64_t r = 0; r < ntiles; r += kWgScan) {
+    const uint64_t i = r + threadIdx.x;
+    uint64_t v[3], base[3];
 #pragma unroll
-    for (uint32_t q = 0; q < 3; ++q) {
-      v[q] = i < ntiles ? a.tile_sum[3 * i + q] : 0ull;
-      inc[q] = wave_incl_scan<uint64_t>(v[q]);
-      if (lane_id() == 63) wsum[w][q] = inc[q];
-    }
-    __syncthreads();
+    for (uint32_t q = 0; q < 3; ++q) v[q] = i < ntiles ? a.tile_sum[3 * i + q] : 0ull;
+    block_round1024<3>(v, wsum, carry, base);
 #pragma unroll
-    for (uint32_t q = 0; q < 3; ++q) {
-      uint64_t base = carry[q], tot = carry[q];
-      for (uint32_t x = 0; x < 16; ++x) {
-        if (x < w) base += wsum[x][q];
-        tot += wsum[x][q];
-      }
-      if (i < ntiles) a.tile_pre[3 * i + q] = base + inc[q] - v[q];
-      carry[q] = tot;
-    }
-    __syncthreads();
+    for (uint32_t q = 0; q < 3; ++q)
+      if (i < ntiles) a.tile_pre[3 * i + q] = base[q];
   }
-  if (t == 1023) {
-    const uint64_t tot[3] = {carry[0], carry[1], carry[2]};
-#pragma unroll
-    for (uint32_t q = 0; q < 3; ++q) a.stats[q] = tot[q];
-    uint32_t err = 0;
-    if (tot[1] > 0xFFFFFFFFull || tot[2] > 0xFFFFFFFFull) err |= LSMBLK_ERR_OVERFLOW;
-    if (tot[0] > a.entry_cap || tot[1] > a.key_cap || tot[2] > a.val_cap) err |= LSMBLK_ERR_CAPACITY;
-    if (!err) {
-      a.okey_off[tot[0]] = uint32_t(tot[1]);
-      a.oval_off[tot[0]] = uint32_t(tot[2]);
-    }
-    or_err(a.stats, err);
-  }
-}
-
-// Copy len bytes src -> dst by the whole wave (wave-uniform arguments): lane l moves 16-B
-// pieces l, l + 64, ... (unaligned loads/stores, 1 KiB of contiguous bytes per instruction);
-// the lane holding a final piece under 16 bytes copies it bytewise.
-__device__ __forceinline__ void wave_copy(uint8_t* dst, const uint8_t* src, uint64_t len) {
-  for (uint64_t o = 16ull * lane_id(); o < len; o += 1024) {
-    if (o + 16 <= len) {
-      *reinterpret_cast<u32x4*>(dst + o) = *reinterpret_cast<const u32x4*>(src + o);
-    } else {
-      for (uint64_t x = o; x < len; ++x) dst[x] = src[x];
-    }
-  }
+  if (threadIdx.x == 1023)
+    publish_totals(a.stats, carry, TotalCaps{a.entry_cap, a.key_cap, a.val_cap}, a.okey_off, a.oval_off, kSentIfClean);
 }
 
 // Output offsets and ts per kept entry; key and value bytes by runs: consecutive kept entries
@@ -4030,8 +3951,8 @@ __global__ __launch_bounds__(256) void filt_write_kernel(FiltArgs a) {
       const uint32_t e = rest ? s + uint32_t(__builtin_ctzll(rest)) : 64u;  // run = lanes [s, e)
       const uint32_t ks = __builtin_amdgcn_readlane(ki, s), ke = __builtin_amdgcn_readlane(ki + kl, e - 1);
       const uint32_t vs = __builtin_amdgcn_readlane(vi, s), ve = __builtin_amdgcn_readlane(vi + vl, e - 1);
-      wave_copy(a.okeys + lane64(ko, s), a.keys + ks, ke - ks);
-      wave_copy(a.ovals + lane64(vo, s), a.vals + vs, ve - vs);
+      wave_copy_bytes(a.okeys + lane64(ko, s), a.keys + ks, ke - ks);
+      wave_copy_bytes(a.ovals + lane64(vo, s), a.vals + vs, ve - vs);
       mask = e >= 64 ? 0ull : mask & (~0ull << e);
     }
   }

@@ -95,14 +95,15 @@ struct SstArgs {
   const uint64_t* cstats;   // block CRC stage stats
 };
 
-// One workgroup: file sizes and their exclusive scan (rounds of 1024 SSTs).
+// One workgroup: file sizes and their exclusive scan (the rounds form of the workgroup scan,
+// lsmblk_dev.hpp: rounds of kWgScan SSTs).
 __global__ __launch_bounds__(1024) void sst_layout_kernel(SstArgs a) {
   const uint32_t t = threadIdx.x, w = t >> 6;
   __shared__ uint64_t wsum[16];
   uint64_t carry = 0;
   uint32_t err = 0;
   if (t == 0) err = uint32_t(a.mstats[3] | a.cstats[3]);
-  for (uint32_t r = 0; r < a.nsst; r += 1024) {
+  for (uint32_t r = 0; r < a.nsst; r += kWgScan) {
     const uint32_t s = r + t;
     uint64_t len = 0;
     if (s < a.nsst) {
@@ -113,17 +114,8 @@ __global__ __launch_bounds__(1024) void sst_layout_kernel(SstArgs a) {
       len = dl + ml + 4 + bloom_geom(a.sst_ent[s + 1] - a.sst_ent[s]).nbytes + 1 + 4 + 4;
       if (dl > 0xFFFFFFFFull || dl + ml + 4 > 0xFFFFFFFFull) err |= LSMBLK_ERR_OVERFLOW;  // u32 offsets
     }
-    const uint64_t inc = wave_incl_scan<uint64_t>(len);
-    if (lane_id() == 63) wsum[w] = inc;
-    __syncthreads();
-    uint64_t base = carry, tot = carry;
-    for (uint32_t x = 0; x < 16; ++x) {
-      if (x < w) base += wsum[x];
-      tot += wsum[x];
-    }
-    if (s < a.nsst) a.file_off[s] = base + inc - len;
-    carry = tot;
-    __syncthreads();
+    const uint64_t base = block_round1024(len, wsum, carry);
+    if (s < a.nsst) a.file_off[s] = base;
   }
   for (uint32_t d = 32; d >= 1; d >>= 1) err |= __shfl_xor(err, d, 64);
   __shared__ uint32_t werr[16];
@@ -136,7 +128,7 @@ __global__ __launch_bounds__(1024) void sst_layout_kernel(SstArgs a) {
     a.stats[0] = a.nsst;
     a.stats[1] = carry;
     if (carry > a.files_cap) e |= LSMBLK_ERR_CAPACITY;
-    if (e) atomicOr(reinterpret_cast<unsigned long long*>(a.stats + 3), (unsigned long long)e);
+    or_err(a.stats, e);
   }
 }
 
@@ -376,7 +368,7 @@ __global__ __launch_bounds__(256) void seek_kernel(SeekArgs a) {
     if (!found) res = lo;
   } while (false);
   a.idx[q] = res;
-  if (err) atomicOr(reinterpret_cast<unsigned long long*>(a.stats + 3), (unsigned long long)err);
+  or_err(a.stats, err);
 }
 
 }  // namespace

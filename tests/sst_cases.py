@@ -53,8 +53,9 @@ def kernel_constants(path=None):
 
 
 C = kernel_constants()
-# sst_layout_kernel scans the file sizes in rounds of its 1024 threads (`r += 1024`, a literal
-# there) and carries the running total from round to round
+# sst_layout_kernel scans the file sizes in rounds of its 1024 threads (`r += kWgScan`, the
+# workgroup scan's width in lsmblk_dev.hpp, tied to 16 waves by a static_assert there) and carries
+# the running total from round to round (block_round1024)
 LAYOUT_ROUND = 1024
 LAYOUT_NSST = (1, LAYOUT_ROUND - 1, LAYOUT_ROUND, LAYOUT_ROUND + 1, 2 * LAYOUT_ROUND, 2 * LAYOUT_ROUND + 1,
                2 * LAYOUT_ROUND + 452)  # the last: a third round partly filled (2500 today)
