@@ -22,9 +22,10 @@
 //                   next block's loads in flight: keys/values staged into LDS, headers written
 //                   by entry lanes, value chunks moved in place with 16-B LDS accesses, the
 //                   block image flushed with 16-B stores.
-//   emit_block_kernel  the same block body in single-wave workgroups, workgroup j emitting blocks
-//                   j, j + grid, ... in dispatch order, nothing prefetched (the default emit
-//                   launch; LSMBLK_DEBUG_EMIT_MODE selects).
+//   emit_block_kernel  the same block body in single-wave workgroups, workgroup j emitting the blocks
+//                   of slots j, j + grid, ... in dispatch order (eight neighbouring blocks per XCD
+//                   within each 64 workgroups), nothing prefetched (the default emit launch;
+//                   LSMBLK_DEBUG_EMIT_MODE selects).
 // Blocks or batches that exceed the LDS fast paths take per-entry-lane "simple" paths
 // that read/write global memory directly (same results, slower).
 #include "lsmblk_dev.hpp"
@@ -82,6 +83,10 @@ constexpr uint32_t kLB = 2;  // decode: 2 measured 1 % faster per step than 1, 4
 // its uses).  Round 2: 2 and 4 spilled beside the next block's prefetch; round 6: 124 / 128 VGPRs, no
 // spill, emit 1.715 / 1.705 / 1.698 ms at 1 / 2 / 4 (alternating, one box).
 constexpr uint32_t kEB = LSMBLK_XEB;
+// emit_block_kernel's own: at 2 it fits 80 VGPRs (6 waves per SIMD, 24 single-wave workgroups per
+// CU); at 4 it takes 95 (20 per CU).  U's encode stage 1.79-1.80 against 1.83 ms (DESIGN.md section 6,
+// "Encode stage").
+constexpr uint32_t kEBBlock = 2;
 
 
 // LDS per single-wave workgroup is exactly 8 KiB, so 20 blocks are resident per CU (5 waves per
@@ -1608,9 +1613,48 @@ __device__ __forceinline__ void walk_segment(const PlanArgs& a, const PlanKeys& 
     uint32_t pmin = kAlcpLcp;     // running min of alcp over (s, window start)
     bool direct = false;
     uint32_t sp = 0, sl = 0;      // key_s (direct compares only)
-    for (uint32_t j0 = s;; j0 += 64) {
+    // The anchored pass: the window [s, s + 64) with the block's first entry on lane 0, so that a
+    // block of at most 64 entries costs one min-scan, one sum-scan and one ballot, and the next
+    // block is anchored again (a window on a fixed grid holds ~2 block ends at U's 31.7 entries per
+    // block, and every end costs a further scan pair in the loop below).  Only the common case: no
+    // out-of-order pair, u32 arithmetic.  Anything else, and a block that runs past lane 63, goes to
+    // the carried-window loop below -- from j0 = s with nothing done, or from j0 = s + 64 with
+    // (carry, pmin) as that loop would have left them.
+    uint32_t j0 = s;
+    const uint32_t aend = s1 - s < 64 ? s1 : s + 64;
+    need(s, aend);
+    if (!(diag_mask(a.skip) & (1u << 17))) {
+      const bool valid = s + l < s1;
+      uint32_t r = 0, al = kAlcpLcp;  // (lane 0: the min identity, its prefix is 0)
+      if (valid) {
+        const uint32_t x = (s + l - S0) & (kRing - 1);
+        r = CR[x];
+        if (l) al = CA[x];
+      }
+      if (narrow && __ballot((al & kAlcpUnsorted) || (valid && r >= (1u << 25) - 16)) == 0) {
+        const uint32_t mn = wave_incl_min31(al);
+        const uint32_t g32 = valid ? r + 16 - (l ? mn : 0u) : 0u;
+        const uint32_t i32 = wave_incl_scan32(g32);
+        const uint32_t b32 = 2 + i32 - g32;
+        const uint64_t m = __ballot(l && (!valid || b32 + r + 14 > uint32_t(bs)));
+        if (m) {
+          const uint32_t f = uint32_t(__builtin_ctzll(m));
+          const uint32_t size = uint32_t(__builtin_amdgcn_readlane(b32, f));
+          sink(s, s + f, size, nb, bytes);
+          ++nb;
+          bytes += size;
+          s += f;
+          continue;
+        }
+        // no stop: 64 valid entries, the block is still open
+        carry = 2 + uint64_t(uint32_t(__builtin_amdgcn_readlane(i32, 63)));
+        pmin = uint32_t(__builtin_amdgcn_readlane(mn, 63));
+        j0 = s + 64;
+      }
+    }
+    for (bool asked = j0 == s;; j0 += 64, asked = false) {
       const uint32_t wend = s1 - j0 < 64 ? s1 : j0 + 64;
-      need(j0, wend);
+      if (!asked) need(j0, wend);
       if (diag_mask(a.skip) & (1u << 17)) {  // ablation: consume the window as one block, no scans
         const uint32_t x = (j0 + l - S0) & (kRing - 1);
         const uint32_t rr = j0 + l < s1 ? CR[x] + CA[x] : 0u;
@@ -2479,35 +2523,68 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void e
   raise_err(a.stats, err);
 }
 
-// Single-wave workgroups in dispatch order: workgroup j emits blocks j, j + grid, ... (one block
-// each up to kEmitGridMax blocks).  Nothing is prefetched across blocks; the overlap comes from the
-// many independent workgroups resident on a CU (95 VGPRs, no scratch, 6384 B of LDS: 20 per CU, 5
-// waves per SIMD, capped by the registers).  Three dependent rounds of loads per block: the block
+// Single-wave workgroups in dispatch order (one block each up to kEmitGridMax blocks, then strides
+// of the grid).  Nothing is prefetched across blocks; the overlap comes from the many independent
+// workgroups resident on a CU (at most 80 VGPRs, no scratch, 6384 B of LDS: 24 per CU, 6 waves per
+// SIMD, capped by the registers).  Three dependent rounds of loads per block: the block
 // tables (scalar), then the first 64 entries' offsets / ts together with the offsets of the
 // block's end entry (the block's byte bounds: lane 0's entry is its start), then the staging
 // loads.  The body is emit_kernel's (emit_phase1, emit_finish), so are the rules for a block that
 // is not fast or whose table entry is refused.
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void emit_block_kernel(EmitArgs a0) {
+//
+// Block order: consecutive workgroups are dispatched round-robin over the 8 XCDs, so under the
+// identity order neighbouring blocks -- which share the 128-B lines at their common edge in the
+// key, value and output streams -- run under different L2s.  Within every whole group of 64
+// consecutive workgroups, workgroup t of the group takes the group's block 8 (t mod 8) + t / 8:
+// XCD x gets the eight neighbouring blocks 8 x .. 8 x + 7.  The map permutes each group's 64 slots
+// among themselves at every stride, and the last, partial group of a grid that is no multiple of
+// 64 keeps the identity, so every block below `lim` is emitted exactly once for any grid.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(6))) void emit_block_kernel(EmitArgs a0) {
   const EmitArgs a = resolve(a0);
   __shared__ EmitBlockLds L;
   const uint32_t l = lane_id();
-  const uint64_t nblk = uni64(a.stats[3]) & kPlanFatal ? 0 : uni64(a.stats[0]);
-  const uint64_t lim = nblk < a.blk_cap ? nblk : (a.blk_cap ? a.blk_cap - 1 : 0);  // blk_off[bi+1] must exist
-  if (blockIdx.x >= lim) return;
-  uint32_t err = 0;
-  const uintptr_t kaddr = reinterpret_cast<uintptr_t>(a.keys), vaddr = reinterpret_cast<uintptr_t>(a.vals);
   cu32_t* const kfirst = kconst(a.blk_first);
   cu64_t* const koff = kconst(a.blk_off);
-  for (uint64_t bi = blockIdx.x; bi < lim; bi += gridDim.x) {
+  const uint32_t group = blockIdx.x & ~63u, t = blockIdx.x & 63u;
+  const uint32_t slot = group + 64 <= gridDim.x ? 8 * (t & 7) + (t >> 3) : t;
+  struct Tab {
+    uint32_t s, e;
+    uint64_t O, size;
+  };
+  auto tables = [&](uint64_t bi, Tab& T) {
+    T.s = kfirst[bi];
+    T.e = kfirst[bi + 1];
+    T.O = koff[bi];
+    T.size = a.blk_sz ? uint64_t(kconst(a.blk_sz)[bi]) : koff[bi + 1] - T.O;
+  };
+  // The first block's table loads go out beside the stats load, not after it, wherever the tables
+  // are known to hold that index without the block count: blk_first and blk_sz have a0.n + 1 entries
+  // (the host's bound on the entries), blk_off blk_cap.  What they hold past the plan's blocks is
+  // never used.
+  const uint64_t b0 = uint64_t(group) + slot;
+  const bool early = b0 + 1 < a.blk_cap && b0 + 1 <= a0.n;
+  Tab T0{};
+  if (early) tables(b0, T0);
+  const uint64_t nblk = uni64(a.stats[3]) & kPlanFatal ? 0 : uni64(a.stats[0]);
+  const uint64_t lim = nblk < a.blk_cap ? nblk : (a.blk_cap ? a.blk_cap - 1 : 0);  // blk_off[bi+1] must exist
+  if (group >= lim) return;
+  uint32_t err = 0;
+  const uintptr_t kaddr = reinterpret_cast<uintptr_t>(a.keys), vaddr = reinterpret_cast<uintptr_t>(a.vals);
+  for (uint64_t gb = group; gb < lim; gb += gridDim.x) {
+    const uint64_t bi = gb + slot;
+    if (bi >= lim) continue;  // (the slot of a group that `lim` cuts)
+    Tab T;
+    if (early && gb == group) T = T0;
+    else tables(bi, T);
     EmitMeta m;  // (as emit_kernel's meta1: a table entry that is not s <= e <= n is refused, none of its entries read)
     m.bi = bi;
-    m.s = kfirst[bi];
-    m.e = kfirst[bi + 1];
+    m.s = T.s;
+    m.e = T.e;
     m.bad = m.e < m.s || uint64_t(m.e) > a.n;
     if (m.bad) m.s = m.e = 0;
     m.n = m.e - m.s;
-    m.O = koff[bi];
-    m.size = a.blk_sz ? uint64_t(kconst(a.blk_sz)[bi]) : koff[bi + 1] - m.O;
+    m.O = T.O;
+    m.size = T.size;
     // a block off the fast path: beyond the LDS image -> flagged for emit_big_kernel; refused -> error
     auto not_fast = [&] {
       if (m.bad) err |= LSMBLK_ERR_INTERNAL;
@@ -2569,7 +2646,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void em
     EmitRecReg R = {};
     const uint32_t data_len = emit_phase1<false>(a, L, R, B, pf, eh, et, ncs, err);
     wave_sync();
-    emit_finish<kEB>(a, L, R, B, data_len, ncs, eh, et);
+    emit_finish<kEBBlock>(a, L, R, B, data_len, ncs, eh, et);
   }
   raise_err(a.stats, err);
 }
