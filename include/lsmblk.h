@@ -725,7 +725,8 @@ int lsmblk_lsm_get_batch(lsmblk_ctx* ctx, const uint8_t* files, const uint64_t* 
 /* The read side's range read (scan_with_ts, src/lsm_storage.rs:446-550) over the opened set of the
  * point lookups: per SST the raw range scan (lsmblk_sst_scan_batch), across SSTs lsmblk_merge_batch
  * with the scans' seg_start as run_start, then the reader's view at read_ts
- * (lsmblk_read_filter_batch). */
+ * (lsmblk_read_filter_batch).  A batch of ranges over a whole LSM view, with any number of tables
+ * per range, is one call of lsmblk_lsm_scan_batch (below). */
 
 /* Bound kinds of q_bound: bits 0-1 the lower bound, bits 2-3 the upper bound (std::ops::Bound). */
 #define LSMBLK_BOUND_UNBOUNDED 0u
@@ -799,6 +800,76 @@ int lsmblk_sst_scan_batch(lsmblk_ctx* ctx, const uint8_t* files, const uint64_t*
 int lsmblk_read_filter_batch(lsmblk_ctx* ctx, const lsmblk_kv_stream* in, const uint32_t* seg_start,
                              const uint64_t* seg_ts, uint32_t nseg, const lsmblk_kv_stream* out,
                              uint32_t* out_seg_start, uint64_t* stats, void* stream);
+
+/* ------------------------------------------------------------------ LSM range scans (device) */
+/* LsmStorageInner::scan_with_ts (src/lsm_storage.rs:446-550) below the memtables, for a batch of
+ * ranges over an LSM view of the opened set (the lsmblk_lsm_view of lsmblk_lsm_get_batch, checked on
+ * the device by the same check before anything else runs).  The memtable iterators stay on the host.
+ *
+ * Sources of a range, in priority order (MergeIterator::create's index order): every L0 table, in l0
+ * order, that passes range_overlap(lower, upper, first_key, last_key) (:142-167, :474-502), then
+ * level by level every table of the level, in table order, that passes it (:504-538).  A level's
+ * tables are in key order and do not overlap (check_sst_valid, src/iterators/concat_iterator.rs:82-93),
+ * so one run per passing table yields what the level's SstConcatIterator yields after
+ * create_and_seek_to_key / the Excluded skip (concat_iterator.rs:50-80): the tables before the seek's
+ * table hold nothing at or after the bound, and the tables after the last passing one nothing within
+ * the upper bound.
+ * Per table: the run is exactly that table's lsmblk_sst_scan_batch range for the same bounds and
+ * kinds, begin and end rules included (flags 0: the reference landing; LSMBLK_SCAN_MVCC: the corrected
+ * landing).  LSMBLK_SCAN_NO_FILTER has no meaning across sources, and it and every other flag bit
+ * return LSMBLK_E_INVAL.
+ * Merge: MergeIterator's (LSMBLK_MERGE_RUNS, src/iterators/merge_iterator.rs:59-184), as in
+ * lsmblk_lsm_get_batch: for every user key, all versions of the lowest-priority-index run that holds
+ * the key, in that run's order, keys ascending.  The as-written TwoMergeIterator nesting of
+ * scan_with_ts (:541-542) is NOT reproduced, as in the point read.
+ * Reader's view: with q_ts != NULL the merged range q is cut by the rule of lsmblk_read_filter_batch
+ * at read_ts = q_ts[q]: merged entry i is kept iff ts[i] <= read_ts, its value is not empty, and i is
+ * the range's first merged entry or key[i-1] != key[i] or ts[i-1] > read_ts.  So a key whose owning
+ * run has no visible version yields nothing even when a later source holds one, and a tombstone in
+ * the owning run hides the key.  LsmIterator::new's untested first position
+ * (src/lsm_iterator.rs:29-43) is not reproduced: the end bound holds for every entry.  With
+ * q_ts == NULL the output is the merged stream itself (res[q].n == res[q].merged). */
+typedef struct {           /* 32 bytes */
+  uint32_t status;         /* LSMBLK_SCAN_OK (n > 0) or LSMBLK_SCAN_EMPTY */
+  uint32_t sources;        /* tables of the view that passed range_overlap and were scanned */
+  uint64_t raw;            /* entries of all those tables' raw scans */
+  uint64_t merged;         /* entries MergeIterator yields over them (all versions of every owned key) */
+  uint64_t n;              /* entries written to out for this range */
+} lsmblk_lsm_scan_result;
+
+/* nq ranges: range q = lower key lkeys[lkey_off[q] .. lkey_off[q+1]), upper key
+ * ukeys[ukey_off[q] .. ukey_off[q+1]), kinds q_bound[q] (as lsmblk_sst_scan_batch), read_ts q_ts[q].
+ *   sub_cap    the most table scans the batch may expand into (< 2^31); the context workspace is sized
+ *              from nq, sub_cap and raw->entry_cap alone, nothing is read back, the call is asynchronous
+ *   raw        required when out is given (NULL with out: LSMBLK_E_INVAL): receives the per-table raw
+ *              scans back to back, ordered by range and then by source -- the scratch the merge reads.
+ *              NULL: only the table scans are sized
+ *   out        NULL: sizes only.  Else the final entries range after range in query order, with the
+ *              bytes lsmblk_decode_batch_ex gives for them (any alignment)
+ *   seg_start  u32[nq+1], required: each range's first entry in out
+ *   nq == 0    writes seg_start[0] and the first word of both offsets arrays of raw and out
+ * stats (u64[LSMBLK_LSM_SCAN_STATS_WORDS]): [0] out entries [1] out key bytes [2] out value bytes
+ * [3] error flags [4] raw entries [5] raw key bytes [6] raw value bytes [7] table scans expanded.
+ * CAPACITY carries the required sizes and nothing is written to the stream that was too small:
+ *   [7] > sub_cap          no scan runs: only [7] and [3] are meaningful, every res[q] is EMPTY with
+ *                          zero counts, seg_start is all zero
+ *   else [4..6] > raw's    (or raw == NULL) [4..7] are valid, [0..2] are zero; res[q].sources and
+ *                          res[q].raw are valid, merged and n zero, seg_start all zero
+ *   else [0..2] > out's    every word, res and seg_start are valid; out's sizes never exceed raw's
+ * Other flags: SEGMENTS / MALFORMED from the view check (as lsmblk_lsm_get_batch: no scan runs, every
+ * res[q] EMPTY with zero counts, seg_start all zero); SEGMENTS for a bound kind of 3 and EMPTY_KEY for
+ * an empty key with a bounded kind (that range is empty, no source); MALFORMED when a visited block
+ * breaks the decode rules: the whole range is empty with sources, raw, merged and n all zero -- never
+ * a partial merge -- while raw and [4..6] still hold its healthy tables' scans; OVERFLOW when a total
+ * does not fit u32.  Every walk and search is bounded by entry, block, table and run counts. */
+#define LSMBLK_LSM_SCAN_STATS_WORDS 8
+int lsmblk_lsm_scan_batch(lsmblk_ctx* ctx, const uint8_t* files, const uint64_t* file_off, uint32_t nsst,
+                          const lsmblk_sst_desc* desc, const lsmblk_sst_index* index, const lsmblk_lsm_view* view,
+                          const uint8_t* lkeys, const uint32_t* lkey_off, const uint8_t* ukeys,
+                          const uint32_t* ukey_off, const uint32_t* q_bound, const uint64_t* q_ts, uint64_t nq,
+                          uint32_t flags, uint64_t sub_cap, lsmblk_lsm_scan_result* res,
+                          const lsmblk_kv_stream* raw, const lsmblk_kv_stream* out, uint32_t* seg_start,
+                          uint64_t* stats, void* stream);
 
 #ifdef __cplusplus
 }

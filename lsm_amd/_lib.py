@@ -49,6 +49,7 @@ LSMBLK_SCAN_EMPTY = 1
 LSMBLK_SCAN_RANGE_OUT = 2
 LSMBLK_SCAN_NO_FILTER = 1
 LSMBLK_SCAN_MVCC = 2
+LSMBLK_LSM_SCAN_STATS_WORDS = 8
 LSMBLK_DEBUG_SCAN_UNITS = 11
 LSMBLK_DEBUG_EMIT_MODE = 12
 
@@ -111,6 +112,11 @@ class ScanResultC(ctypes.Structure):
     """lsmblk_scan_result (32 bytes)."""
     _fields_ = [("status", U32), ("blk0", U32), ("ent0", U32), ("blk1", U32), ("ent1", U32), ("blocks", U32),
                 ("n", U64)]
+
+
+class LsmScanResultC(ctypes.Structure):
+    """lsmblk_lsm_scan_result (32 bytes)."""
+    _fields_ = [("status", U32), ("sources", U32), ("raw", U64), ("merged", U64), ("n", U64)]
 
 
 # (name, restype, argtypes) for every symbol of include/lsmblk.h
@@ -189,6 +195,8 @@ SIGNATURES = [
     ("lsmblk_sst_scan_batch", I, [P, P, P, U32, P, P, P, P, P, P, P, P, U64, U32, P, ctypes.POINTER(KVStreamC), P, P,
                                   P]),
     ("lsmblk_read_filter_batch", I, [P, ctypes.POINTER(KVStreamC), P, P, U32, ctypes.POINTER(KVStreamC), P, P, P]),
+    ("lsmblk_lsm_scan_batch", I, [P, P, P, U32, P, P, ctypes.POINTER(LsmViewC), P, P, P, P, P, P, U64, U32, U64, P,
+                                  ctypes.POINTER(KVStreamC), ctypes.POINTER(KVStreamC), P, P, P]),
 ]
 
 

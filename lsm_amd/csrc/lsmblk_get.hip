@@ -29,6 +29,10 @@
 //                           tested on every entry, the landing included -- LsmIterator::new's untested
 //                           first position (lsm_iterator.rs:29-43) belongs to the merged iterator and
 //                           is not reproduced per SST.  Kernels: see "scan" below
+//   lsmblk_lsm_scan_batch   scan_with_ts below the memtables (lsm_storage.rs:446-550) for a batch of ranges
+//                           over an LSM view: every passing table scanned by the scan kernels, a
+//                           segmented merge per range, the reader's view.  Kernels: see "the LSM range
+//                           scan" below
 #include "lsmblk_dev.hpp"
 
 namespace {
@@ -1070,7 +1074,17 @@ struct ScanArgs {
   uint64_t* ucnt;    // 3 per unit: counts, then their exclusive prefixes
   uint32_t budget;
   uint64_t* stats;
+  // lsmblk_lsm_scan_batch's table scans (the kernels' kSub form): their count, known on the device
+  // only, and per scan the range whose bound keys and kinds it takes; q_sst, res, qbad and seg_start
+  // are per scan
+  const uint64_t* nq_dev;
+  const uint32_t* parent;
 };
+template <bool kSub>
+__device__ __forceinline__ uint64_t scan_nq(const ScanArgs& a) {
+  if constexpr (kSub) return uni64(*a.nq_dev);
+  else return a.nq;
+}
 
 // Block b of the SST through its LDS image S (up to kGetLdsBlock bytes) or a bounds-checked
 // descriptor: fn(image, block bytes) -> its verdict; false when the index record's range is not a
@@ -1126,6 +1140,7 @@ __device__ __forceinline__ bool scan_lu(const uint8_t* F, const lsmblk_sst_index
   });
 }
 
+template <bool kSub>
 __global__ __launch_bounds__(64 * kGetWaves) void scan_bounds_kernel(ScanArgs a) {
   __shared__ __attribute__((aligned(16))) uint8_t img[kGetWaves][kGetImg];
   const uint32_t l = lane_id();
@@ -1135,10 +1150,14 @@ __global__ __launch_bounds__(64 * kGetWaves) void scan_bounds_kernel(ScanArgs a)
   const uint32_t ulead = uint32_t(reinterpret_cast<uintptr_t>(a.ukeys) & 3);
   uint32_t err = 0;
   const uint64_t stride = uint64_t(gridDim.x) * kGetWaves;
-  for (uint64_t qi = uint64_t(blockIdx.x) * kGetWaves + wave_id(); qi < a.nq; qi += stride) {
+  const uint64_t nq = scan_nq<kSub>(a);
+  for (uint64_t qi = uint64_t(blockIdx.x) * kGetWaves + wave_id(); qi < nq; qi += stride) {
     uint32_t status = LSMBLK_SCAN_EMPTY, b0 = kNone, e0 = kNone, b1 = kNone, e1 = kNone, nb = 0;
+    bool malformed = false;
     do {
-      const uint32_t s = uni(a.q_sst[qi]), bnd = uni(a.q_bound[qi]);
+      uint64_t pq = qi;  // the range whose bounds this scan takes
+      if constexpr (kSub) pq = uni(a.parent[qi]);
+      const uint32_t s = uni(a.q_sst[qi]), bnd = uni(a.q_bound[pq]);
       const uint32_t lk = bnd & 3, uk = (bnd >> 2) & 3;
       if (s >= a.nsst || lk == 3 || uk == 3) {
         err |= LSMBLK_ERR_SEGMENTS;
@@ -1146,12 +1165,12 @@ __global__ __launch_bounds__(64 * kGetWaves) void scan_bounds_kernel(ScanArgs a)
       }
       uint32_t l0 = 0, l1 = 0, u0 = 0, u1 = 0;
       if (lk) {
-        l0 = uni(a.lkey_off[qi]);
-        l1 = uni(a.lkey_off[qi + 1]);
+        l0 = uni(a.lkey_off[pq]);
+        l1 = uni(a.lkey_off[pq + 1]);
       }
       if (uk) {
-        u0 = uni(a.ukey_off[qi]);
-        u1 = uni(a.ukey_off[qi + 1]);
+        u0 = uni(a.ukey_off[pq]);
+        u1 = uni(a.ukey_off[pq + 1]);
       }
       if ((lk && l1 <= l0) || (uk && u1 <= u0)) {
         err |= LSMBLK_ERR_EMPTY_KEY;
@@ -1247,6 +1266,7 @@ __global__ __launch_bounds__(64 * kGetWaves) void scan_bounds_kernel(ScanArgs a)
       }
       if (bad) {
         err |= LSMBLK_ERR_MALFORMED;
+        malformed = true;
         break;
       }
       if (b > nblk) b = nblk;
@@ -1270,7 +1290,8 @@ __global__ __launch_bounds__(64 * kGetWaves) void scan_bounds_kernel(ScanArgs a)
       r.blocks = nb;
       r.n = 0;
       a.res[qi] = r;
-      a.qbad[qi] = 0;
+      // (a table scan of the LSM scan marks a malformed search as well: its range takes no partial merge)
+      a.qbad[qi] = kSub && malformed ? 1u : 0u;
     }
   }
   raise_err(a.stats, err);
@@ -1278,10 +1299,12 @@ __global__ __launch_bounds__(64 * kGetWaves) void scan_bounds_kernel(ScanArgs a)
 
 static_assert(kScanWg == kWgScan, "share1024 / block_excl1024 (lsmblk_dev.hpp) serve a workgroup of kWgScan threads");
 
+template <bool kSub>
 __global__ __launch_bounds__(kScanWg) void scan_units_kernel(ScanArgs a) {
   __shared__ uint64_t wsum[16];
+  const uint64_t nq = scan_nq<kSub>(a);
   uint64_t q0, q1;
-  share1024(a.nq, q0, q1);
+  share1024(nq, q0, q1);
   uint64_t sum = 0, tot;
   for (uint64_t q = q0; q < q1; ++q) sum += a.res[q].blocks;
   (void)block_excl1024(sum, wsum, tot);
@@ -1294,7 +1317,7 @@ __global__ __launch_bounds__(kScanWg) void scan_units_kernel(ScanArgs a) {
     o += (a.res[q].blocks + bpu - 1) / bpu;
   }
   if (threadIdx.x == 0) {
-    a.ubase[a.nq] = uint32_t(tot);  // <= nq + budget < 2^32
+    a.ubase[nq] = uint32_t(tot);  // <= nq + budget < 2^32
     a.hdr[0] = tot;
     a.hdr[1] = bpu;
   }
@@ -1331,14 +1354,15 @@ __device__ __forceinline__ bool unit_blocks(const ScanArgs& a, uint32_t q, uint3
   return true;
 }
 
+template <bool kSub>
 __global__ __launch_bounds__(64 * kGetWaves) void scan_count_kernel(ScanArgs a) {
   __shared__ __attribute__((aligned(16))) uint8_t img[kGetWaves][kGetImg];
   const uint32_t l = lane_id();
   uint8_t* const S = img[wave_id()];
-  const uint64_t nu = uni64(a.hdr[0]), stride = uint64_t(gridDim.x) * kGetWaves;
+  const uint64_t nu = uni64(a.hdr[0]), stride = uint64_t(gridDim.x) * kGetWaves, nq = scan_nq<kSub>(a);
   uint32_t err = 0;
   for (uint64_t u = uint64_t(blockIdx.x) * kGetWaves + wave_id(); u < nu; u += stride) {
-    const uint32_t q = unit_query(a.ubase, a.nq, uint32_t(u));
+    const uint32_t q = unit_query(a.ubase, nq, uint32_t(u));
     uint64_t ne = 0, kb = 0, vb = 0;
     const bool ok = unit_blocks(a, q, uint32_t(u), S, [&](const auto& im, const BlkHdr& h, uint32_t w0, uint32_t w1) {
       bool bad = false;
@@ -1373,14 +1397,15 @@ __global__ __launch_bounds__(64 * kGetWaves) void scan_count_kernel(ScanArgs a) 
   raise_err(a.stats, err);
 }
 
+template <bool kSub>
 __global__ __launch_bounds__(kScanWg) void scan_offsets_kernel(ScanArgs a) {
   __shared__ uint64_t wsum[16][3];
-  const uint64_t nu = a.hdr[0];
+  const uint64_t nu = a.hdr[0], nq = scan_nq<kSub>(a);
   uint64_t u0, u1;
   share1024(nu, u0, u1);
   // a share's first range by search, then forward with the units (ubase is non-decreasing)
   auto first_query = [&](uint64_t u) {
-    uint64_t lo = 0, hi = a.nq;  // the last q with ubase[q] <= u
+    uint64_t lo = 0, hi = nq;  // the last q with ubase[q] <= u
     while (lo < hi) {
       const uint64_t mid = (lo + hi + 1) / 2;
       if (a.ubase[mid] <= u) lo = mid;
@@ -1395,7 +1420,7 @@ __global__ __launch_bounds__(kScanWg) void scan_offsets_kernel(ScanArgs a) {
   if (u0 < u1 && masked) {
     uint64_t q = first_query(u0);
     for (uint64_t u = u0; u < u1; ++u) {
-      while (q + 1 < a.nq && a.ubase[q + 1] <= u) ++q;
+      while (q + 1 < nq && a.ubase[q + 1] <= u) ++q;
       if (!a.qbad[q])
         for (uint32_t k = 0; k < 3; ++k) sum[k] += a.ucnt[3 * u + k];
     }
@@ -1414,7 +1439,7 @@ __global__ __launch_bounds__(kScanWg) void scan_offsets_kernel(ScanArgs a) {
   } else if (u0 < u1) {
     uint64_t q = first_query(u0);
     for (uint64_t u = u0; u < u1; ++u) {
-      while (q + 1 < a.nq && a.ubase[q + 1] <= u) ++q;
+      while (q + 1 < nq && a.ubase[q + 1] <= u) ++q;
       const bool live = !a.qbad[q];
       for (uint32_t k = 0; k < 3; ++k) {
         const uint64_t v = a.ucnt[3 * u + k];
@@ -1432,11 +1457,11 @@ __global__ __launch_bounds__(kScanWg) void scan_offsets_kernel(ScanArgs a) {
   }
   __threadfence_block();
   __syncthreads();  // the unit prefixes are written
-  for (uint64_t q = threadIdx.x; q <= a.nq; q += kScanWg) {
+  for (uint64_t q = threadIdx.x; q <= nq; q += kScanWg) {
     const uint32_t ub = a.ubase[q];
     const uint64_t st = ub < nu ? a.ucnt[3 * uint64_t(ub)] : tot[0];
     a.seg_start[q] = uint32_t(st);
-    if (q < a.nq) {
+    if (q < nq) {
       const uint32_t ue = a.ubase[q + 1];
       const uint64_t n = (ue < nu ? a.ucnt[3 * uint64_t(ue)] : tot[0]) - st;
       lsmblk_scan_result r = a.res[q];
@@ -1466,14 +1491,15 @@ __device__ __forceinline__ void quarter_copy(uint8_t* dst, const Img& im, uint32
   if (x < len) dst[x] = uint8_t(im.u8(src + x));
 }
 
+template <bool kSub>
 __global__ __launch_bounds__(64 * kGetWaves) void scan_emit_kernel(ScanArgs a) {
   __shared__ __attribute__((aligned(16))) uint8_t img[kGetWaves][kGetImg];
   if (a.stats[3] & (LSMBLK_ERR_CAPACITY | LSMBLK_ERR_OVERFLOW)) return;
   const uint32_t l = lane_id(), sub = l & 15, grp = l >> 4;
   uint8_t* const S = img[wave_id()];
-  const uint64_t nu = uni64(a.hdr[0]), stride = uint64_t(gridDim.x) * kGetWaves;
+  const uint64_t nu = uni64(a.hdr[0]), stride = uint64_t(gridDim.x) * kGetWaves, nq = scan_nq<kSub>(a);
   for (uint64_t u = uint64_t(blockIdx.x) * kGetWaves + wave_id(); u < nu; u += stride) {
-    const uint32_t q = unit_query(a.ubase, a.nq, uint32_t(u));
+    const uint32_t q = unit_query(a.ubase, nq, uint32_t(u));
     if (uni(a.qbad[q])) continue;
     uint64_t ei = uni64(a.ucnt[3 * u]), ko = uni64(a.ucnt[3 * u + 1]), vo = uni64(a.ucnt[3 * u + 2]);
     (void)unit_blocks(a, q, uint32_t(u), S, [&](const auto& im, const BlkHdr& h, uint32_t w0, uint32_t w1) {
@@ -1511,6 +1537,444 @@ __global__ __launch_bounds__(64 * kGetWaves) void scan_emit_kernel(ScanArgs a) {
       }
       return true;
     });
+  }
+}
+
+// The five scan launches: lsmblk_sst_scan_batch's (kSub false) and, under their own names in the
+// kernel log, the table scans of lsmblk_lsm_scan_batch (kSub true).
+template <bool kSub>
+void launch_scan(const ScanArgs& a, uint32_t qgrid, uint32_t ugrid, bool emit, hipStream_t st) {
+  LSM_LAUNCH_NAMED(kSub ? "lsm_scan_sub_bounds_kernel" : "scan_bounds_kernel", scan_bounds_kernel<kSub>, dim3(qgrid),
+                   dim3(64 * kGetWaves), 0, st, a);
+  LSM_LAUNCH_NAMED(kSub ? "lsm_scan_sub_units_kernel" : "scan_units_kernel", scan_units_kernel<kSub>, dim3(1), dim3(kScanWg), 0,
+                   st, a);
+  LSM_LAUNCH_NAMED(kSub ? "lsm_scan_sub_count_kernel" : "scan_count_kernel", scan_count_kernel<kSub>, dim3(ugrid),
+                   dim3(64 * kGetWaves), 0, st, a);
+  LSM_LAUNCH_NAMED(kSub ? "lsm_scan_sub_offsets_kernel" : "scan_offsets_kernel", scan_offsets_kernel<kSub>, dim3(1),
+                   dim3(kScanWg), 0, st, a);
+  if (emit)
+    LSM_LAUNCH_NAMED(kSub ? "lsm_scan_sub_emit_kernel" : "scan_emit_kernel", scan_emit_kernel<kSub>, dim3(ugrid),
+                     dim3(64 * kGetWaves), 0, st, a);
+}
+
+// ---------------------------------------------------------------- the LSM range scan
+// lsmblk_lsm_scan_batch: scan_with_ts below the memtables for a batch of ranges over an LSM view.
+//   lsm_view_check_kernel     the point read's, unchanged
+//   lsm_scan_expand_kernel    <false> one wave per range: the tables that pass range_overlap, counted
+//                             (L0: every table by its own lane; a level: the span between two k-ary
+//                             searches, then every table of the span by its own lane)
+//   lsm_scan_subs_kernel      one workgroup: sbase = exclusive scan of the counts, the total against
+//                             sub_cap -> nsub, the table scans that run (0: refused view, sub_cap short)
+//   lsm_scan_expand_kernel    <true> the same walk, writing (range, table) of every table scan
+//   lsm_scan_sub_*_kernel     the five scan kernels over the table scans -> the raw stream, run after
+//                             run, and sseg = every run's first raw entry
+//   lsm_scan_rank_kernel      the segmented merge: one raw entry per lane, its merge rank among the
+//                             runs of its range by a search in every other run -> slot
+//   lsm_scan_offsets_kernel   one workgroup: the three-component scan over the slots in merged order,
+//                             totals, capacity / overflow, key_off / val_off, seg_start, res
+//   lsm_scan_gather_kernel    16 lanes per kept entry: key, value, ts -> out
+struct LsmScanArgs {
+  const uint8_t* files;
+  const lsmblk_sst_desc* desc;
+  uint32_t nsst;
+  const uint32_t* l0;
+  uint32_t nl0, nlevel;
+  const uint32_t* level_sst;
+  const uint32_t* level_start;
+  const uint8_t* lkeys;
+  const uint32_t* lkey_off;
+  const uint8_t* ukeys;
+  const uint32_t* ukey_off;
+  const uint32_t* q_bound;
+  const uint64_t* q_ts;  // null: the merged stream itself
+  uint64_t nq, sub_cap;
+  lsmblk_lsm_scan_result* res;
+  const uint8_t* rkeys;  // the raw stream (read by the merge)
+  const uint32_t* rkey_off;
+  const uint32_t* rval_off;
+  const uint8_t* rvals;
+  const uint64_t* rts;
+  uint32_t has_raw, has_out;
+  uint8_t* okeys;
+  uint32_t* okey_off;
+  uint8_t* ovals;
+  uint32_t* oval_off;
+  uint64_t* ots;
+  uint64_t entry_cap, key_cap, val_cap;
+  uint32_t* seg_start;
+  uint64_t* stats;
+  // workspace
+  uint32_t* vflag;        // the view check's verdict
+  uint64_t* nsub;         // [0] table scans that run
+  uint64_t* sstats;       // the table scans' stats (4 words)
+  uint32_t* scnt;         // nq: tables per range
+  uint32_t* sbase;        // nq + 1: first table scan of every range
+  uint32_t* pbad;         // nq: a block on the range's path is malformed
+  uint32_t* mcnt;         // nq: merged entries
+  uint32_t* sub_q;        // sub_cap: the table scan's range ...
+  uint32_t* sub_sst;      // ... and table
+  uint32_t* sseg;         // sub_cap + 1: first raw entry of every run
+  const uint32_t* sbad;   // sub_cap: the table scans' qbad
+  uint32_t* slot;         // slot_cap: merged position -> raw entry + 1 (0: not kept)
+  uint32_t* opre;         // slot_cap + 1: kept entries before the merged position
+  uint64_t slot_cap;
+};
+
+// Order of raw key x[0 .. lx) against the lane's own key y[0 .. ly), whose image is (yhi, ylo): the
+// leading 16 bytes as images (independent loads, one round trip) decide unless they tie.
+__device__ __forceinline__ int lane_cmp_img2(const uint8_t* x, uint32_t lx, const uint8_t* y, uint32_t ly, uint64_t yhi,
+                                             uint64_t ylo) {
+  uint64_t hi = 0, lo = 0;
+#pragma unroll
+  for (uint32_t j = 0; j < 16; ++j) {
+    const uint64_t b = j < lx ? x[j] : 0;
+    if (j < 8) hi |= b << (56 - 8 * j);
+    else lo |= b << (56 - 8 * (j - 8));
+  }
+  if (hi != yhi) return hi < yhi ? -1 : 1;
+  if (lo != ylo) return lo < ylo ? -1 : 1;
+  return lane_cmp2(x, lx, y, ly);
+}
+
+// One wave per range, grid-strided, over the view's tables in priority order; every candidate table
+// is tested by its own lane with range_overlap (lsm_storage.rs:142-167) against the descriptor's
+// first and last key.  A level's tables are ordered and disjoint (the view check), so the tables
+// whose last key lies before the lower bound are a prefix of the level and those whose first key
+// lies within the upper bound are one too: a level of more than 64 tables is cut to that span by two
+// k-ary searches first.  kFill false: scnt[q] = the passing tables; true: their (range, table) pairs
+// from sbase[q] on.
+template <bool kFill>
+__global__ __launch_bounds__(64 * kGetWaves) void lsm_scan_expand_kernel(LsmScanArgs a) {
+  const uint32_t l = lane_id();
+  if constexpr (kFill) {
+    if (uni64(a.nsub[0]) == 0) return;
+  }
+  const bool run = uni(*a.vflag) == 0;
+  const uint32_t llead = uint32_t(reinterpret_cast<uintptr_t>(a.lkeys) & 3);
+  const uint32_t ulead = uint32_t(reinterpret_cast<uintptr_t>(a.ukeys) & 3);
+  uint32_t err = 0;
+  const uint64_t stride = uint64_t(gridDim.x) * kGetWaves;
+  for (uint64_t qi = uint64_t(blockIdx.x) * kGetWaves + wave_id(); qi < a.nq; qi += stride) {
+    uint32_t cnt = 0;
+    const uint32_t base = kFill ? uni(a.sbase[qi]) : 0u;
+    do {
+      if (!run) break;
+      const uint32_t bnd = uni(a.q_bound[qi]);
+      const uint32_t lk = bnd & 3, uk = (bnd >> 2) & 3;
+      if (lk == 3 || uk == 3) {
+        err |= LSMBLK_ERR_SEGMENTS;
+        break;
+      }
+      uint32_t l0 = 0, l1 = 0, u0 = 0, u1 = 0;
+      if (lk) {
+        l0 = uni(a.lkey_off[qi]);
+        l1 = uni(a.lkey_off[qi + 1]);
+      }
+      if (uk) {
+        u0 = uni(a.ukey_off[qi]);
+        u1 = uni(a.ukey_off[qi + 1]);
+      }
+      if ((lk && l1 <= l0) || (uk && u1 <= u0)) {
+        err |= LSMBLK_ERR_EMPTY_KEY;
+        break;
+      }
+      const QKey lo{make_rsrc_exact(const_cast<uint8_t*>(a.lkeys - llead), lk ? (llead + l1 + 3) & ~3u : 0u), llead + l0, l1 - l0};
+      const QKey up{make_rsrc_exact(const_cast<uint8_t*>(a.ukeys - ulead), uk ? (ulead + u1 + 3) & ~3u : 0u), ulead + u0, u1 - u0};
+      uint64_t lhi = 0, llo = 0, uhi = 0, ulo = 0;
+      if (lk) query_image(lo, lhi, llo);
+      if (uk) query_image(up, uhi, ulo);
+      // table t's first key against the upper bound, its last key against the lower bound
+      auto first_in = [&](uint32_t t) {
+        const lsmblk_sst_desc* d = a.desc + t;
+        const int c = lane_cmp_img(a.files + d->first_key_pos, d->first_key_len, up, uhi, ulo);
+        return uk == LSMBLK_BOUND_EXCLUDED ? c < 0 : c <= 0;
+      };
+      auto last_before = [&](uint32_t t) {
+        const lsmblk_sst_desc* d = a.desc + t;
+        const int c = lane_cmp_img(a.files + d->last_key_pos, d->last_key_len, lo, lhi, llo);
+        return lk == LSMBLK_BOUND_EXCLUDED ? c <= 0 : c < 0;
+      };
+      // ids[i0 .. i1): each tested by its own lane, the passing ones taken in order
+      auto take = [&](const uint32_t* ids, uint32_t i0, uint32_t i1) {
+        for (uint32_t c = i0; c < i1; c += 64) {
+          const uint32_t i = c + l, t = i < i1 ? ids[i] : kNone;
+          bool ok = t < a.nsst && a.desc[t].nblk != 0;  // (the view check refuses any other)
+          if (ok && uk) ok = first_in(t);
+          if (ok && lk) ok = !last_before(t);
+          const uint64_t m = __ballot(ok);
+          if constexpr (kFill) {
+            const uint64_t x = uint64_t(base) + cnt + uint32_t(__builtin_popcountll(m & ((1ull << l) - 1)));
+            if (ok && x < a.sub_cap) {
+              a.sub_q[x] = uint32_t(qi);
+              a.sub_sst[x] = t;
+            }
+          }
+          cnt += uint32_t(__builtin_popcountll(m));
+        }
+      };
+      take(a.l0, 0, a.nl0);
+      for (uint32_t lv = 0; lv < a.nlevel; ++lv) {
+        const uint32_t t0 = uni(a.level_start[lv]), n = uni(a.level_start[lv + 1]) - t0;
+        const uint32_t* ls = a.level_sst + t0;
+        uint32_t s0 = 0, s1 = n;
+        if (n > 64) {
+          if (lk) s0 = kary_first_false(0, n, [&](uint32_t i) { return ls[i] < a.nsst && last_before(ls[i]); });
+          if (uk) s1 = kary_first_false(s0, n, [&](uint32_t i) { return ls[i] < a.nsst && first_in(ls[i]); });
+        }
+        take(ls, s0, s1);
+      }
+    } while (false);
+    if constexpr (!kFill) {
+      if (l == 0) a.scnt[qi] = cnt;
+    }
+  }
+  if constexpr (!kFill) raise_err(a.stats, err);
+}
+
+// sbase = exclusive scan of the ranges' table counts (the share form of the workgroup scan); the
+// total is stats[7], and the table scans run only when it fits sub_cap.
+__global__ __launch_bounds__(kScanWg) void lsm_scan_subs_kernel(LsmScanArgs a) {
+  __shared__ uint64_t wsum[16];
+  uint64_t q0, q1;
+  share1024(a.nq, q0, q1);
+  uint64_t sum = 0, tot;
+  for (uint64_t q = q0; q < q1; ++q) sum += a.scnt[q];
+  uint64_t o = block_excl1024(sum, wsum, tot);
+  const bool fits = tot <= a.sub_cap;  // (sub_cap < 2^31: the positions fit u32)
+  for (uint64_t q = q0; q < q1; ++q) {
+    a.sbase[q] = fits ? uint32_t(o) : 0u;
+    o += a.scnt[q];
+  }
+  if (threadIdx.x == 0) {
+    a.sbase[a.nq] = fits ? uint32_t(tot) : 0u;
+    a.nsub[0] = fits ? tot : 0;
+    a.stats[7] = tot;
+    if (!fits) or_err(a.stats, LSMBLK_ERR_CAPACITY);
+  }
+}
+
+// The segmented merge.  Work items are 64-entry tiles of the raw stream, one entry per lane, so a
+// huge range spreads over as many waves as a batch of small ones.  Entry e is entry i of run r of
+// range q; for every other run r' of q a bytewise, ts-agnostic binary search (a shorter key is less)
+// gives lb(r') = its entries below key(e) or ub(r') = its entries not above it, and
+//   pos = i + sum over r' < r of ub(r') + sum over r' > r of lb(r')
+// is e's rank in the stable merge of q's runs by key, a bijection onto q's [0, raw).  e is owned iff
+// no r' < r holds its key (lb == ub there): MergeIterator yields exactly the owned entries, keys
+// ascending, a key's versions in its owner's order.  The reader's rule needs merged entry pos - 1:
+// a key's owned versions are contiguous at the head of its group in merged order (the owner is the
+// lowest run holding the key, and ub places every lower run's entries before them), so the merged
+// predecessor of an owned entry with the same key is the same run's entry i - 1, and one with
+// another key changes nothing in the rule whoever owns it.
+__global__ __launch_bounds__(256) void lsm_scan_rank_kernel(LsmScanArgs a) {
+  const uint64_t nsub = uni64(a.nsub[0]);
+  if (!nsub || (a.sstats[3] & (LSMBLK_ERR_CAPACITY | LSMBLK_ERR_OVERFLOW))) return;
+  const uint64_t nraw = uni(a.sseg[nsub]);
+  if (nraw > a.slot_cap) return;  // (a raw stream that passed its capacity check fits the slots)
+  const uint32_t l = lane_id();
+  const uint64_t tiles = (nraw + 63) / 64, stride = uint64_t(gridDim.x) * 4;
+  auto klen = [&](uint64_t x) { return a.rkey_off[x + 1] - a.rkey_off[x]; };
+  for (uint64_t tile = uint64_t(blockIdx.x) * 4 + wave_id(); tile < tiles; tile += stride) {
+    const uint64_t e = tile * 64 + l;
+    const bool on = e < nraw;
+    uint32_t q = kNone;
+    bool owned = false;
+    if (on) {
+      uint64_t lo = 0, hi = nsub - 1;  // the run: the first r with sseg[r + 1] > e
+      while (lo < hi) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (a.sseg[mid + 1] <= e) lo = mid + 1;
+        else hi = mid;
+      }
+      const uint32_t r = uint32_t(lo);
+      q = a.sub_q[r];
+      const uint32_t r0 = a.sbase[q], r1 = a.sbase[q + 1];
+      const uint8_t* const kp = a.rkeys + a.rkey_off[e];
+      const uint32_t kl = klen(e);
+      uint64_t khi = 0, klo = 0;
+#pragma unroll
+      for (uint32_t j = 0; j < 16; ++j) {
+        const uint64_t b = j < kl ? kp[j] : 0;
+        if (j < 8) khi |= b << (56 - 8 * j);
+        else klo |= b << (56 - 8 * (j - 8));
+      }
+      auto cmp = [&](uint64_t x) { return lane_cmp_img2(a.rkeys + a.rkey_off[x], klen(x), kp, kl, khi, klo); };
+      uint64_t pos = e - a.sseg[r];
+      owned = true;
+      for (uint32_t r2 = r0; r2 < r1; ++r2) {
+        const uint64_t x0 = a.sseg[r2], x1 = a.sseg[r2 + 1];
+        if (r2 == r || x1 <= x0) continue;
+        const bool upper = r2 < r;  // ub for the runs before r, lb for those after
+        uint64_t p;
+        // the run's first and last key first: most runs of a range lie wholly on one side of a key
+        const int cf = cmp(x0);
+        if (cf > 0 || (cf == 0 && !upper)) {
+          p = x0;
+        } else {
+          const int cl = x1 - x0 > 1 ? cmp(x1 - 1) : cf;
+          if (cl < 0 || (cl == 0 && upper)) {
+            p = x1;
+          } else {  // the first x of (x0, x1 - 1] with key(x) > key(e) (ub) / >= key(e) (lb)
+            uint64_t s = x0 + 1, t = x1 - 1;
+            while (s < t) {
+              const uint64_t mid = s + (t - s) / 2;
+              const int c = cmp(mid);
+              if (c < 0 || (c == 0 && upper)) s = mid + 1;
+              else t = mid;
+            }
+            p = s;
+          }
+        }
+        pos += p - x0;
+        if (upper && p > x0 && cmp(p - 1) == 0) owned = false;
+      }
+      bool keep = owned;
+      if (keep && a.q_ts) {
+        const uint64_t read_ts = a.q_ts[q];
+        keep = a.rts[e] <= read_ts && a.rval_off[e + 1] > a.rval_off[e];
+        if (keep && e > a.sseg[r] && a.rts[e - 1] <= read_ts)
+          keep = lane_cmp2(a.rkeys + a.rkey_off[e - 1], klen(e - 1), kp, kl) != 0;
+      }
+      const uint64_t at = uint64_t(a.sseg[r0]) + pos;
+      if (at < nraw) a.slot[at] = keep ? uint32_t(e) + 1 : 0u;
+    }
+    // merged entries: a tile's lanes are in raw order, so a range's lanes are consecutive; its first
+    // lane adds the range's owned lanes
+    const uint64_t om = __ballot(on && owned);
+    const uint32_t qp = __shfl_up(q, 1, 64);
+    const bool head = on && (l == 0 || qp != q);
+    const uint64_t hm = __ballot(head);
+    if (head) {
+      const uint64_t rest = l == 63 ? 0ull : hm >> (l + 1);
+      const uint32_t nxt = rest ? l + 1 + uint32_t(__builtin_ctzll(rest)) : 64u;
+      const uint64_t m = (nxt == 64 ? ~0ull : (1ull << nxt) - 1) & ~((1ull << l) - 1);
+      const uint32_t c = uint32_t(__builtin_popcountll(om & m));
+      if (c) atomicAdd(a.mcnt + q, c);
+    }
+  }
+}
+
+// One workgroup: the ranges' malformed marks, then the three-component exclusive scan (entries, key
+// bytes, value bytes) over the slots in merged order in the share form of the workgroup scan, the
+// totals and flags, the out offsets, and per range seg_start and res.
+__global__ __launch_bounds__(kScanWg) void lsm_scan_offsets_kernel(LsmScanArgs a) {
+  __shared__ uint64_t wsum[16][3];
+  const uint64_t nsub = a.nsub[0];
+  const uint32_t serr = uint32_t(a.sstats[3]);
+  const uint64_t nraw = nsub ? a.sseg[nsub] : 0;
+  // ranked: the raw stream was written and lsm_scan_rank_kernel ran over it
+  const bool ranked = nsub && a.has_raw && !(serr & (LSMBLK_ERR_CAPACITY | LSMBLK_ERR_OVERFLOW)) && nraw <= a.slot_cap;
+  const bool masked = (serr & LSMBLK_ERR_MALFORMED) != 0;
+  if (masked)
+    for (uint64_t s = threadIdx.x; s < nsub; s += kScanWg)
+      if (a.sbad[s]) a.pbad[a.sub_q[s]] = 1;
+  __threadfence_block();
+  __syncthreads();
+  auto qstart = [&](uint64_t q) -> uint64_t { return a.sseg[a.sbase[q]]; };  // q <= nq: sbase[nq] = nsub
+  auto first_query = [&](uint64_t i) {  // the last q with qstart(q) <= i
+    uint64_t lo = 0, hi = a.nq - 1;
+    while (lo < hi) {
+      const uint64_t mid = (lo + hi + 1) / 2;
+      if (qstart(mid) <= i) lo = mid;
+      else hi = mid - 1;
+    }
+    return lo;
+  };
+  uint64_t i0, i1;
+  share1024(ranked ? nraw : 0, i0, i1);
+  // a slot's entry, 0 when it keeps none; a malformed range's slots are cleared on the way
+  uint64_t q = masked && i0 < i1 ? first_query(i0) : 0;
+  uint64_t sum[3] = {0, 0, 0}, tot[3], base[3];
+  for (uint64_t i = i0; i < i1; ++i) {
+    uint32_t s = a.slot[i];
+    if (masked) {
+      while (q + 1 < a.nq && qstart(q + 1) <= i) ++q;
+      if (a.pbad[q]) s = 0;
+    }
+    if (s > nraw) s = 0;
+    if (s != a.slot[i]) a.slot[i] = s;
+    if (s) {
+      sum[0] += 1;
+      sum[1] += a.rkey_off[s] - a.rkey_off[s - 1];
+      sum[2] += a.rval_off[s] - a.rval_off[s - 1];
+    }
+  }
+  block_excl1024<3>(sum, wsum, base, tot);
+  const bool fits = a.has_out && tot[0] <= a.entry_cap && tot[1] <= a.key_cap && tot[2] <= a.val_cap &&
+                    tot[0] <= 0xFFFFFFFFull && tot[1] <= 0xFFFFFFFFull && tot[2] <= 0xFFFFFFFFull;
+  for (uint64_t i = i0; i < i1; ++i) {
+    const uint32_t s = a.slot[i];
+    a.opre[i] = uint32_t(base[0]);
+    if (s) {
+      if (fits) {
+        a.okey_off[base[0]] = uint32_t(base[1]);
+        a.oval_off[base[0]] = uint32_t(base[2]);
+      }
+      base[0] += 1;
+      base[1] += a.rkey_off[s] - a.rkey_off[s - 1];
+      base[2] += a.rval_off[s] - a.rval_off[s - 1];
+    }
+  }
+  if (threadIdx.x == 0) {
+    if (ranked) a.opre[nraw] = uint32_t(tot[0]);
+    const TotalCaps caps = a.has_out ? TotalCaps{a.entry_cap, a.key_cap, a.val_cap} : TotalCaps{~0ull, ~0ull, ~0ull};
+    publish_totals(a.stats, tot, caps, a.has_out ? a.okey_off : nullptr, a.has_out ? a.oval_off : nullptr, kSentIfClean, 0,
+                   /*ovf_entries=*/true);
+    or_err(a.stats, serr);
+    for (uint32_t k = 0; k < 3; ++k) a.stats[4 + k] = a.sstats[k];
+  }
+  __threadfence_block();
+  __syncthreads();  // opre is written
+  for (uint64_t p = threadIdx.x; p <= a.nq; p += kScanWg) {
+    if (p == a.nq) {
+      a.seg_start[p] = ranked ? uint32_t(tot[0]) : 0u;
+      break;
+    }
+    lsmblk_lsm_scan_result r{LSMBLK_SCAN_EMPTY, 0, 0, 0, 0};
+    uint32_t st = 0;
+    if (nsub && !a.pbad[p]) {
+      r.sources = a.sbase[p + 1] - a.sbase[p];
+      r.raw = qstart(p + 1) - qstart(p);
+    }
+    if (ranked) {
+      st = a.opre[qstart(p)];
+      r.n = a.opre[qstart(p + 1)] - st;
+      if (!a.pbad[p]) r.merged = a.mcnt[p];
+      if (r.n) r.status = LSMBLK_SCAN_OK;
+    }
+    a.seg_start[p] = st;
+    a.res[p] = r;
+  }
+}
+
+// len bytes src -> dst by the 16 lanes of a quarter wave (sub = lane & 15), any alignment: 16-B
+// pieces, then the last partial piece one byte per lane (quarter_copy's shape over global memory).
+__device__ __forceinline__ void quarter_copy_glb(uint8_t* dst, const uint8_t* src, uint32_t len, uint32_t sub) {
+  const uint32_t full = len & ~15u;
+  for (uint32_t o = 16 * sub; o < full; o += 256) *reinterpret_cast<u32x4*>(dst + o) = *reinterpret_cast<const u32x4*>(src + o);
+  const uint32_t x = full + sub;
+  if (x < len) dst[x] = src[x];
+}
+
+// A quarter wave per merged position, grid-strided: a kept entry's key, value and ts to its place.
+__global__ __launch_bounds__(256) void lsm_scan_gather_kernel(LsmScanArgs a) {
+  if (a.stats[3] & (LSMBLK_ERR_CAPACITY | LSMBLK_ERR_OVERFLOW)) return;
+  const uint64_t nsub = a.nsub[0];
+  const uint64_t nraw = nsub ? a.sseg[nsub] : 0;
+  if (nraw > a.slot_cap) return;
+  const uint32_t sub = threadIdx.x & 15;
+  const uint64_t stride = uint64_t(gridDim.x) * 16;
+  for (uint64_t i = uint64_t(blockIdx.x) * 16 + (threadIdx.x >> 4); i < nraw; i += stride) {
+    const uint32_t s = a.slot[i];
+    if (!s || s > nraw) continue;
+    const uint64_t e = s - 1, oi = a.opre[i];
+    if (oi >= a.entry_cap) continue;
+    const uint32_t kl = a.rkey_off[e + 1] - a.rkey_off[e], vl = a.rval_off[e + 1] - a.rval_off[e];
+    const uint32_t ko = a.okey_off[oi], vo = a.oval_off[oi];
+    // (the totals passed the capacity check: a place past a capacity is not written)
+    if (uint64_t(ko) + kl > a.key_cap || uint64_t(vo) + vl > a.val_cap) continue;
+    quarter_copy_glb(a.okeys + ko, a.rkeys + a.rkey_off[e], kl, sub);
+    quarter_copy_glb(a.ovals + vo, a.rvals + a.rval_off[e], vl, sub);
+    if (sub == 0) a.ots[oi] = a.rts[e];
   }
 }
 
@@ -1687,15 +2151,193 @@ int lsmblk_sst_scan_batch(lsmblk_ctx* c, const uint8_t* files, const uint64_t* f
   a.ucnt = reinterpret_cast<uint64_t*>(c->sws + o_cnt);
   a.budget = uint32_t(budget);
   a.stats = stats;
+  a.nq_dev = nullptr;
+  a.parent = nullptr;
   int cus = 256;
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
   const uint64_t cap = uint64_t(cus > 0 ? cus : 256) * 8;
   const uint64_t qw = (nq + kGetWaves - 1) / kGetWaves, uw = (units + kGetWaves - 1) / kGetWaves;
-  LSM_LAUNCH(scan_bounds_kernel, dim3(uint32_t(qw < cap ? qw : cap)), dim3(64 * kGetWaves), 0, st, a);
-  LSM_LAUNCH(scan_units_kernel, dim3(1), dim3(kScanWg), 0, st, a);
-  LSM_LAUNCH(scan_count_kernel, dim3(uint32_t(uw < cap ? uw : cap)), dim3(64 * kGetWaves), 0, st, a);
-  LSM_LAUNCH(scan_offsets_kernel, dim3(1), dim3(kScanWg), 0, st, a);
-  if (out) LSM_LAUNCH(scan_emit_kernel, dim3(uint32_t(uw < cap ? uw : cap)), dim3(64 * kGetWaves), 0, st, a);
+  launch_scan<false>(a, uint32_t(qw < cap ? qw : cap), uint32_t(uw < cap ? uw : cap), out != nullptr, st);
+  return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
+}
+
+int lsmblk_lsm_scan_batch(lsmblk_ctx* c, const uint8_t* files, const uint64_t* file_off, uint32_t nsst,
+                          const lsmblk_sst_desc* desc, const lsmblk_sst_index* index, const lsmblk_lsm_view* view,
+                          const uint8_t* lkeys, const uint32_t* lkey_off, const uint8_t* ukeys, const uint32_t* ukey_off,
+                          const uint32_t* q_bound, const uint64_t* q_ts, uint64_t nq, uint32_t flags, uint64_t sub_cap,
+                          lsmblk_lsm_scan_result* res, const lsmblk_kv_stream* raw, const lsmblk_kv_stream* out,
+                          uint32_t* seg_start, uint64_t* stats, void* stream) {
+  if (!c || !stats || !seg_start || !view || (flags & ~LSMBLK_SCAN_MVCC) || (out && !raw)) return LSMBLK_E_INVAL;
+  if ((view->nl0 && !view->l0) || (view->nlevel && (!view->level_start || !view->level_sst)) ||
+      uint64_t(view->nl0) + view->nlevel >= 0xFFFFFFFFull)
+    return LSMBLK_E_INVAL;
+  if (nq && (!q_bound || !lkey_off || !ukey_off || !res || (nsst && (!files || !file_off || !desc)))) return LSMBLK_E_INVAL;
+  for (const lsmblk_kv_stream* s : {raw, out})
+    if (s && (!s->key_off || !s->val_off || (s->entry_cap && !s->ts) || (s->key_cap && !s->keys) || (s->val_cap && !s->vals)))
+      return LSMBLK_E_INVAL;
+  if ((reinterpret_cast<uintptr_t>(files) & 15) || (reinterpret_cast<uintptr_t>(index) & 15) || nq > 0x7FFFFFFFull ||
+      sub_cap > 0x7FFFFFFFull)
+    return LSMBLK_E_INVAL;
+  std::lock_guard<std::mutex> g(c->mu);
+  DeviceGuard dg(c->device, c);
+  if (!dg.ok) return LSMBLK_E_HIP;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (hipMemsetAsync(stats, 0, LSMBLK_LSM_SCAN_STATS_WORDS * 8, st) != hipSuccess) return LSMBLK_E_HIP;
+  if (nq == 0) {
+    if (hipMemsetAsync(seg_start, 0, 4, st) != hipSuccess) return LSMBLK_E_HIP;
+    for (const lsmblk_kv_stream* s : {raw, out})
+      if (s && (hipMemsetAsync(s->key_off, 0, 4, st) != hipSuccess || hipMemsetAsync(s->val_off, 0, 4, st) != hipSuccess))
+        return LSMBLK_E_HIP;
+    return LSMBLK_OK;
+  }
+  // workspace, sized by nq, sub_cap, the unit budget and raw's entry capacity alone:
+  //   head (vflag, nsub, the table scans' stats) | pbad | mcnt | scnt | sbase | sub_q | sub_sst | sseg | table scan
+  //   results | the scan kernels' ubase | qbad | hdr | ucnt | slot | opre
+  const uint64_t budget = c->scan_units, units = sub_cap + budget;
+  const uint64_t slot_cap = raw ? (raw->entry_cap < 0xFFFFFFFFull ? raw->entry_cap : 0xFFFFFFFFull) : 0;
+  uint64_t need = 0;
+  auto carve = [&](uint64_t bytes) {
+    const uint64_t o = need;
+    need += (bytes + 255) & ~255ull;
+    return o;
+  };
+  const uint64_t o_head = carve(256), o_pbad = carve(4 * nq), o_mcnt = carve(4 * nq), zero_end = need;
+  const uint64_t o_scnt = carve(4 * nq), o_sbase = carve(4 * (nq + 1)), o_subq = carve(4 * sub_cap), o_subs = carve(4 * sub_cap);
+  const uint64_t o_sseg = carve(4 * (sub_cap + 1)), o_sres = carve(sizeof(lsmblk_scan_result) * sub_cap);
+  const uint64_t o_ubase = carve(4 * (sub_cap + 1)), o_qbad = carve(4 * sub_cap), o_hdr = carve(256), o_cnt = carve(24 * units);
+  const uint64_t o_slot = carve(4 * slot_cap), o_opre = carve(4 * (slot_cap + 1));
+  int rc;
+  if (need > c->sws_cap && (rc = grow(st, &c->sws, &c->sws_cap, need, 1))) return rc;
+  uint8_t* const W = c->sws;
+  if (hipMemsetAsync(W, 0, zero_end, st) != hipSuccess) return LSMBLK_E_HIP;
+  // (a slot no entry ranks to -- only files that are not in key order leave one -- keeps nothing)
+  if (slot_cap && hipMemsetAsync(W + o_slot, 0, 4 * slot_cap, st) != hipSuccess) return LSMBLK_E_HIP;
+  auto u32p = [&](uint64_t o) { return reinterpret_cast<uint32_t*>(W + o); };
+  uint64_t* const head = reinterpret_cast<uint64_t*>(W + o_head);
+
+  LsmGetArgs v{};
+  v.files = files;
+  v.file_off = file_off;
+  v.nsst = nsst;
+  v.desc = desc;
+  v.index = index;
+  v.l0 = view->l0;
+  v.nl0 = view->nl0;
+  v.nlevel = view->nlevel;
+  v.level_sst = view->level_sst;
+  v.level_start = view->level_start;
+  v.nq = nq;
+  v.stats = stats;
+  v.vflag = u32p(o_head);
+
+  LsmScanArgs a{};
+  a.files = files;
+  a.desc = desc;
+  a.nsst = nsst;
+  a.l0 = view->l0;
+  a.nl0 = view->nl0;
+  a.nlevel = view->nlevel;
+  a.level_sst = view->level_sst;
+  a.level_start = view->level_start;
+  a.lkeys = lkeys;
+  a.lkey_off = lkey_off;
+  a.ukeys = ukeys;
+  a.ukey_off = ukey_off;
+  a.q_bound = q_bound;
+  a.q_ts = q_ts;
+  a.nq = nq;
+  a.sub_cap = sub_cap;
+  a.res = res;
+  if (raw) {
+    a.rkeys = raw->keys;
+    a.rkey_off = raw->key_off;
+    a.rvals = raw->vals;
+    a.rval_off = raw->val_off;
+    a.rts = raw->ts;
+    a.has_raw = 1;
+  }
+  if (out) {
+    a.okeys = out->keys;
+    a.okey_off = out->key_off;
+    a.ovals = out->vals;
+    a.oval_off = out->val_off;
+    a.ots = out->ts;
+    a.entry_cap = out->entry_cap;
+    a.key_cap = out->key_cap;
+    a.val_cap = out->val_cap;
+    a.has_out = 1;
+  }
+  a.seg_start = seg_start;
+  a.stats = stats;
+  a.vflag = u32p(o_head);
+  a.nsub = head + 1;
+  a.sstats = head + 4;
+  a.pbad = u32p(o_pbad);
+  a.mcnt = u32p(o_mcnt);
+  a.scnt = u32p(o_scnt);
+  a.sbase = u32p(o_sbase);
+  a.sub_q = u32p(o_subq);
+  a.sub_sst = u32p(o_subs);
+  a.sseg = u32p(o_sseg);
+  a.sbad = u32p(o_qbad);
+  a.slot = u32p(o_slot);
+  a.opre = u32p(o_opre);
+  a.slot_cap = slot_cap;
+
+  // the table scans: range_overlap already passed (NO_FILTER), bounds and kinds of the scan's range
+  ScanArgs s{};
+  s.files = files;
+  s.file_off = file_off;
+  s.nsst = nsst;
+  s.desc = desc;
+  s.index = index;
+  s.q_sst = a.sub_sst;
+  s.lkeys = lkeys;
+  s.lkey_off = lkey_off;
+  s.ukeys = ukeys;
+  s.ukey_off = ukey_off;
+  s.q_bound = q_bound;
+  s.nq = 0;
+  s.flags = flags | LSMBLK_SCAN_NO_FILTER;
+  s.res = reinterpret_cast<lsmblk_scan_result*>(W + o_sres);
+  if (raw) {
+    s.okeys = raw->keys;
+    s.okey_off = raw->key_off;
+    s.ovals = raw->vals;
+    s.oval_off = raw->val_off;
+    s.ots = raw->ts;
+    s.entry_cap = raw->entry_cap;
+    s.key_cap = raw->key_cap;
+    s.val_cap = raw->val_cap;
+    s.has_out = 1;
+  }
+  s.seg_start = a.sseg;
+  s.ubase = u32p(o_ubase);
+  s.qbad = u32p(o_qbad);
+  s.hdr = reinterpret_cast<uint64_t*>(W + o_hdr);
+  s.ucnt = reinterpret_cast<uint64_t*>(W + o_cnt);
+  s.budget = uint32_t(budget);
+  s.stats = a.sstats;
+  s.nq_dev = a.nsub;
+  s.parent = a.sub_q;
+
+  int cus = 256;
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
+  const uint64_t cap = uint64_t(cus > 0 ? cus : 256) * 8;
+  auto grid = [&](uint64_t items, uint64_t per) {
+    const uint64_t w = (items + per - 1) / per;
+    return dim3(uint32_t(w < 1 ? 1 : (w < cap ? w : cap)));
+  };
+  LSM_LAUNCH(lsm_view_check_kernel, dim3(32), dim3(256), 0, st, v);
+  LSM_LAUNCH_NAMED("lsm_scan_expand_count_kernel", lsm_scan_expand_kernel<false>, grid(nq, kGetWaves), dim3(64 * kGetWaves), 0,
+                   st, a);
+  LSM_LAUNCH(lsm_scan_subs_kernel, dim3(1), dim3(kScanWg), 0, st, a);
+  LSM_LAUNCH_NAMED("lsm_scan_expand_fill_kernel", lsm_scan_expand_kernel<true>, grid(nq, kGetWaves), dim3(64 * kGetWaves), 0,
+                   st, a);
+  launch_scan<true>(s, grid(sub_cap, kGetWaves).x, grid(units, kGetWaves).x, raw != nullptr, st);
+  if (raw) LSM_LAUNCH(lsm_scan_rank_kernel, grid(slot_cap, 256), dim3(256), 0, st, a);
+  LSM_LAUNCH(lsm_scan_offsets_kernel, dim3(1), dim3(kScanWg), 0, st, a);
+  if (out) LSM_LAUNCH(lsm_scan_gather_kernel, grid(slot_cap, 16), dim3(256), 0, st, a);
   return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
 }
 

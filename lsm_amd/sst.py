@@ -15,7 +15,9 @@
                     (sst, lower, upper) range scans with every version in range
                     (lsmblk_sst_scan_batch), filtered to a reader's view by batch.read_filter; over an
                     LsmView (L0 tables and levels of the set) batches of keys with one answer per
-                    key, get_with_ts below the memtables (lsmblk_lsm_get_batch)
+                    key, get_with_ts below the memtables (lsmblk_lsm_get_batch), and batches of
+                    ranges with each range's merged reader's view, scan_with_ts below the memtables
+                    (lsmblk_lsm_scan_batch)
 
 Device work goes through liblsmblk.so; the footer / section parsing here is host logic that mirrors
 the reference's own (the CRC-32 of those small sections is zlib's, which is crc32fast's).
@@ -28,9 +30,9 @@ import torch
 
 from . import batch
 from ._lib import (LSMBLK_BOUND_EXCLUDED, LSMBLK_BOUND_INCLUDED, LSMBLK_BOUND_UNBOUNDED, LSMBLK_E_CAPACITY,
-                   LSMBLK_GET_FOUND, LSMBLK_GET_MVCC, LSMBLK_GET_NO_FILTER, LSMBLK_LSM_GET_NEWEST, LSMBLK_SCAN_MVCC,
-                   LSMBLK_SCAN_NO_FILTER, GetResultC, LsmBlkError, LsmGetResultC, LsmViewC, ScanResultC, SstDescC,
-                   SstIndexC, check, lib)
+                   LSMBLK_GET_FOUND, LSMBLK_GET_MVCC, LSMBLK_GET_NO_FILTER, LSMBLK_LSM_GET_NEWEST,
+                   LSMBLK_LSM_SCAN_STATS_WORDS, LSMBLK_SCAN_MVCC, LSMBLK_SCAN_NO_FILTER, GetResultC, LsmBlkError,
+                   LsmGetResultC, LsmScanResultC, LsmViewC, ScanResultC, SstDescC, SstIndexC, check, lib)
 
 
 class MemTable:
@@ -227,6 +229,7 @@ ERR_CAPACITY = 2  # LSMBLK_ERR_CAPACITY
 GET_FIELDS = ("status", "blk", "ent", "hit_blk", "hit_ent", "vlen", "ts", "val_pos")
 LSM_GET_FIELDS = ("status", "src", "sst", "hit_blk", "hit_ent", "vlen", "ts", "val_pos", "seeks", "bloom_out")
 SCAN_FIELDS = ("status", "blk0", "ent0", "blk1", "ent1", "blocks", "n")
+LSM_SCAN_FIELDS = ("status", "sources", "raw", "merged", "n")
 BOUND_KINDS = {"unbounded": LSMBLK_BOUND_UNBOUNDED, "included": LSMBLK_BOUND_INCLUDED, "excluded": LSMBLK_BOUND_EXCLUDED}
 
 
@@ -564,3 +567,102 @@ class SstSet:
         rows = [[(kb[ko[i]:ko[i + 1]], int(ts[i]), vb[vo[i]:vo[i + 1]]) for i in range(int(seg[q]), int(seg[q + 1]))]
                 for q in range(nq)]
         return {f: r[f].copy() for f in SCAN_FIELDS}, rows
+
+    # ---- range scans over an LSM view
+    def lsm_scan_into(self, view, lkeys, lkey_off, ukeys, ukey_off, q_bound, q_ts, nq, flags, sub_cap, res, seg_start,
+                      stats, raw: batch.KVStream = None, out: batch.KVStream = None, raw_caps=None, out_caps=None):
+        """Asynchronous lsmblk_lsm_scan_batch over device tensors (no host sync): lkey_off / ukey_off /
+        q_bound / seg_start int32 (u32), q_ts int64 (u64) or None (the merged stream), res uint8[32 nq],
+        stats int64[8]; raw None: the table scans are sized only; out None: sizes only; *_caps =
+        (entry_cap, key_cap, val_cap), default the stream's caps()."""
+        dev = self.device.index
+        batch._need(lkey_off, torch.int32, "lkey_off", dev, nq + 1)
+        batch._need(ukey_off, torch.int32, "ukey_off", dev, nq + 1)
+        batch._need(q_bound, torch.int32, "q_bound", dev, nq)
+        if q_ts is not None:
+            batch._need(q_ts, torch.int64, "q_ts", dev, nq)
+        batch._need(res, torch.uint8, "res", dev, nq * ctypes.sizeof(LsmScanResultC))
+        batch._need(seg_start, torch.int32, "seg_start", dev, nq + 1)
+        batch._need(stats, torch.int64, "stats", dev, LSMBLK_LSM_SCAN_STATS_WORDS)
+        cs = []
+        for s, caps, name in ((raw, raw_caps, "raw"), (out, out_caps, "out")):
+            if s is not None:
+                s.check(dev, name, 0)
+            cs.append(s._c(*(caps if caps is not None else s.caps())) if s is not None else None)
+        cv = view._c()
+        batch._native("lsmblk_lsm_scan_batch", dev, self.stream, batch._ptr(self.files), self.file_off.data_ptr(),
+                      self.nsst, self.desc_t.data_ptr(), batch._ptr(self.index_t), ctypes.byref(cv), lkeys.data_ptr(),
+                      lkey_off.data_ptr(), ukeys.data_ptr(), ukey_off.data_ptr(), q_bound.data_ptr(),
+                      q_ts.data_ptr() if q_ts is not None else None, nq, flags, sub_cap, res.data_ptr(),
+                      ctypes.byref(cs[0]) if cs[0] is not None else None,
+                      ctypes.byref(cs[1]) if cs[1] is not None else None, seg_start.data_ptr(), stats.data_ptr(),
+                      batch._stream_ptr(self.stream, dev))
+
+    def lsm_scan_raw(self, view, lower, upper, lower_kind, upper_kind, read_ts=None, flags=0, sub_cap=None,
+                     raw_caps=None, out_caps=None, raw=None, out=None):
+        """One lsmblk_lsm_scan_batch call -> (results as a numpy record array, seg_start numpy, the raw
+        KVStream or None, the out KVStream or None, stats list); nothing raises on the stats.
+        *_caps = (entries, key bytes, value bytes) of a fresh stream (or of `raw` / `out`, a caller's
+        stream); None: that stream is not passed.  sub_cap None: view_sub_cap(view, nq)."""
+        dev, nq = self.device, len(lower)
+        _, lk, lo, uk, uo, bnd = self.upload_ranges([0] * nq, lower, upper, lower_kind, upper_kind)
+        qt = None
+        if read_ts is not None:
+            ts = np.broadcast_to(np.asarray(read_ts, np.uint64), (nq,)).copy() if nq else np.zeros(1, np.uint64)
+            qt = torch.from_numpy(ts.view(np.int64)).to(dev)
+        res = torch.zeros(max(nq, 1) * ctypes.sizeof(LsmScanResultC), dtype=torch.uint8, device=dev)
+        seg = torch.zeros(nq + 1, dtype=torch.int32, device=dev)
+        stats = torch.zeros(LSMBLK_LSM_SCAN_STATS_WORDS, dtype=torch.int64, device=dev)
+        if raw_caps is not None and raw is None:
+            raw = batch.KVStream.empty(*raw_caps, dev)
+        if out_caps is not None and out is None:
+            out = batch.KVStream.empty(*out_caps, dev)
+        raw = raw if raw_caps is not None else None
+        out = out if out_caps is not None else None
+        self.lsm_scan_into(view, lk, lo, uk, uo, bnd, qt, nq, flags, view_sub_cap(view, nq) if sub_cap is None else sub_cap,
+                           res, seg, stats, raw, out, raw_caps, out_caps)
+        torch.cuda.synchronize(dev)
+        r = res.cpu().numpy().view(np.dtype(LsmScanResultC))[:nq]
+        st = [int(x) & 0xFFFFFFFFFFFFFFFF for x in stats.cpu().tolist()]
+        if not st[3] & (ERR_CAPACITY | 4):
+            if raw is not None:
+                raw.n = st[4]
+            if out is not None:
+                out.n = st[0]
+        return r, seg.cpu().numpy().view(np.uint32), raw, out, st
+
+    def lsm_scan(self, view, lower, upper, *, lower_kind, upper_kind, read_ts=None, mvcc=False, sub_cap=None):
+        """scan_with_ts below the memtables for a batch of ranges over `view`: range i = (lower[i],
+        upper[i]) with the bound kinds, at read_ts[i] (or the scalar read_ts) -> (dict of numpy arrays:
+        status, sources, raw, merged, n; and per range the list of (key, ts, value)).  read_ts None:
+        the merged stream, every version of every key's owning table.  sub_cap defaults to every table
+        of the view for every range, which always fits.  Retries at most once on CAPACITY, relying on
+        which stats words the header declares valid: a short sub_cap reports only [7], a short raw
+        stream [4..7], a short out stream every word (out never needs more than raw)."""
+        nq = len(lower)
+        cap = view_sub_cap(view, nq) if sub_cap is None else sub_cap
+        rc = oc = (64 * nq + 1024, 1024 * nq + 4096, 4096 * nq + 4096)
+        for _ in range(2):
+            r, seg, _, kv, st = self.lsm_scan_raw(view, lower, upper, lower_kind, upper_kind, read_ts,
+                                                  LSMBLK_SCAN_MVCC if mvcc else 0, cap, rc, oc)
+            if st[3] != ERR_CAPACITY:
+                break
+            if st[7] > cap:  # no scan ran: the streams' sizes are still unknown
+                cap = st[7]
+            elif st[4] > rc[0] or st[5] > rc[1] or st[6] > rc[2]:
+                rc = (st[4], st[5], st[6])
+                oc = tuple(max(a, b) for a, b in zip(oc, rc))
+            else:
+                oc = (st[0], st[1], st[2])
+        if st[3]:
+            raise LsmBlkError(lib().lsmblk_stats_status(st[3]), "lsm scan")
+        keys, ko, vals, vo, ts = kv.to_numpy()
+        kb, vb = keys.tobytes(), vals.tobytes()
+        rows = [[(kb[ko[i]:ko[i + 1]], int(ts[i]), vb[vo[i]:vo[i + 1]]) for i in range(int(seg[q]), int(seg[q + 1]))]
+                for q in range(nq)]
+        return {f: r[f].copy() for f in LSM_SCAN_FIELDS}, rows
+
+
+def view_sub_cap(view, nq):
+    """Table scans a batch of nq ranges over the view can expand into at most: every table, every range."""
+    return nq * (len(view.l0) + sum(len(lv) for lv in view.levels))

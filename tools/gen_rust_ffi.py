@@ -12,7 +12,7 @@ STRUCTS = {"lsmblk_builder": "LsmblkBuilder", "lsmblk_block": "LsmblkBlock", "ls
            "lsmblk_kernel_stat": "LsmblkKernelStat", "lsmblk_sst_desc": "LsmblkSstDesc",
            "lsmblk_sst_index": "LsmblkSstIndex", "lsmblk_get_result": "LsmblkGetResult",
            "lsmblk_scan_result": "LsmblkScanResult", "lsmblk_lsm_view": "LsmblkLsmView",
-           "lsmblk_lsm_get_result": "LsmblkLsmGetResult"}
+           "lsmblk_lsm_get_result": "LsmblkLsmGetResult", "lsmblk_lsm_scan_result": "LsmblkLsmScanResult"}
 SCALARS = {"int": "c_int", "uint32_t": "u32", "uint64_t": "u64", "size_t": "usize", "uint8_t": "u8",
            "uint16_t": "u16", "float": "f32", "char": "c_char", "void": "c_void", "int32_t": "i32"}
 
