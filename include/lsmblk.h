@@ -816,8 +816,8 @@ int lsmblk_read_filter_batch(lsmblk_ctx* ctx, const lsmblk_kv_stream* in, const 
  * the upper bound.
  * Per table: the run is exactly that table's lsmblk_sst_scan_batch range for the same bounds and
  * kinds, begin and end rules included (flags 0: the reference landing; LSMBLK_SCAN_MVCC: the corrected
- * landing).  LSMBLK_SCAN_NO_FILTER has no meaning across sources, and it and every other flag bit
- * return LSMBLK_E_INVAL.
+ * landing; LSMBLK_LSM_SCAN_NEWEST: below).  LSMBLK_SCAN_NO_FILTER has no meaning across sources, and it
+ * and every other flag bit return LSMBLK_E_INVAL, with or without the flags above.
  * Merge: MergeIterator's (LSMBLK_MERGE_RUNS, src/iterators/merge_iterator.rs:59-184), as in
  * lsmblk_lsm_get_batch: for every user key, all versions of the lowest-priority-index run that holds
  * the key, in that run's order, keys ascending.  The as-written TwoMergeIterator nesting of
@@ -828,12 +828,33 @@ int lsmblk_read_filter_batch(lsmblk_ctx* ctx, const lsmblk_kv_stream* in, const 
  * run has no visible version yields nothing even when a later source holds one, and a tombstone in
  * the owning run hides the key.  LsmIterator::new's untested first position
  * (src/lsm_iterator.rs:29-43) is not reproduced: the end bound holds for every entry.  With
- * q_ts == NULL the output is the merged stream itself (res[q].n == res[q].merged). */
+ * q_ts == NULL the output is the merged stream itself (res[q].n == res[q].merged).
+ *
+ * LSMBLK_LSM_SCAN_NEWEST (the value of LSMBLK_LSM_GET_NEWEST; with or without LSMBLK_SCAN_MVCC, which
+ * it implies) is the snapshot scan, the range read that lsmblk_lsm_get_batch's NEWEST is for a key.
+ * Sources, table scans, the view check, the sub_cap / raw / out capacity contract, the stats words and
+ * every error report are those of the other modes.
+ *   Landing: the corrected one per table.  An Included / Excluded lower bound begins at a key's first
+ *     version or after its last, and the end rule holds for every entry, so every run holds whole
+ *     version groups.
+ *   Merge: the stable merge of the range's runs by (key ascending bytewise with a shorter key less, ts
+ *     descending, source ordinal ascending, position in the run ascending).  Every raw entry of a
+ *     healthy range is in it: res[q].merged == res[q].raw.  With q_ts == NULL out is that stream --
+ *     every version of every key from every passing table, in snapshot order -- and res[q].n ==
+ *     res[q].merged.
+ *   Reader's view (q_ts != NULL): the rule above over that merged stream.  Per key the row is the
+ *     newest version at or below read_ts over all sources, the lower source ordinal winning an equal
+ *     ts, and a tombstone there hides the key whichever source holds it.
+ *   Precondition: every table's entries are in (key ascending, ts descending) order, as a builder fed
+ *     by a memtable flush or a compaction writes them.  For other files the result is unspecified;
+ *     every walk and search stays bounded as in the other modes. */
+#define LSMBLK_LSM_SCAN_NEWEST 4u
 typedef struct {           /* 32 bytes */
   uint32_t status;         /* LSMBLK_SCAN_OK (n > 0) or LSMBLK_SCAN_EMPTY */
   uint32_t sources;        /* tables of the view that passed range_overlap and were scanned */
   uint64_t raw;            /* entries of all those tables' raw scans */
-  uint64_t merged;         /* entries MergeIterator yields over them (all versions of every owned key) */
+  uint64_t merged;         /* entries MergeIterator yields over them (all versions of every owned key);
+                              LSMBLK_LSM_SCAN_NEWEST: = raw */
   uint64_t n;              /* entries written to out for this range */
 } lsmblk_lsm_scan_result;
 

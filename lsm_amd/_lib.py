@@ -49,6 +49,7 @@ LSMBLK_SCAN_EMPTY = 1
 LSMBLK_SCAN_RANGE_OUT = 2
 LSMBLK_SCAN_NO_FILTER = 1
 LSMBLK_SCAN_MVCC = 2
+LSMBLK_LSM_SCAN_NEWEST = 4
 LSMBLK_LSM_SCAN_STATS_WORDS = 8
 LSMBLK_DEBUG_SCAN_UNITS = 11
 LSMBLK_DEBUG_EMIT_MODE = 12

@@ -1569,7 +1569,8 @@ void launch_scan(const ScanArgs& a, uint32_t qgrid, uint32_t ugrid, bool emit, h
 //   lsm_scan_sub_*_kernel     the five scan kernels over the table scans -> the raw stream, run after
 //                             run, and sseg = every run's first raw entry
 //   lsm_scan_rank_kernel      the segmented merge: one raw entry per lane, its merge rank among the
-//                             runs of its range by a search in every other run -> slot
+//                             runs of its range by a search in every other run -> slot (<true>,
+//                             LSMBLK_LSM_SCAN_NEWEST: the rank by (key, ts descending), no ownership)
 //   lsm_scan_offsets_kernel   one workgroup: the three-component scan over the slots in merged order,
 //                             totals, capacity / overflow, key_off / val_off, seg_start, res
 //   lsm_scan_gather_kernel    16 lanes per kept entry: key, value, ts -> out
@@ -1765,6 +1766,17 @@ __global__ __launch_bounds__(kScanWg) void lsm_scan_subs_kernel(LsmScanArgs a) {
 // lowest run holding the key, and ub places every lower run's entries before them), so the merged
 // predecessor of an owned entry with the same key is the same run's entry i - 1, and one with
 // another key changes nothing in the rule whoever owns it.
+//
+// kNewest (LSMBLK_LSM_SCAN_NEWEST): the merge by (key ascending, ts descending) instead.  The order
+// of raw entry x against e is the key order and, on equal keys, x before e when ts[x] > ts[e]; an
+// equal ts is the tie the run order resolves, as an equal key is above.  Every run is sorted by that
+// order (the precondition), so lb / ub, the shortcut and the search carry over and pos is e's rank
+// in the stable merge by (key, ts descending, run, position), a bijection onto q's [0, raw): every
+// entry is merged, nothing is owned.  The reader's rule needs the merged predecessor: the
+// entries of run r' before e in merged order are [x0, p), those with e's key are contiguous at the end,
+// and p - 1 has the smallest ts of them; the predecessor is the latest of the runs' p - 1 (the own
+// run's is e - 1), so it has e's key and a ts <= read_ts -- e is hidden -- iff some run's p - 1 has.
+template <bool kNewest>
 __global__ __launch_bounds__(256) void lsm_scan_rank_kernel(LsmScanArgs a) {
   const uint64_t nsub = uni64(a.nsub[0]);
   if (!nsub || (a.sstats[3] & (LSMBLK_ERR_CAPACITY | LSMBLK_ERR_OVERFLOW))) return;
@@ -1797,7 +1809,33 @@ __global__ __launch_bounds__(256) void lsm_scan_rank_kernel(LsmScanArgs a) {
         if (j < 8) khi |= b << (56 - 8 * j);
         else klo |= b << (56 - 8 * (j - 8));
       }
-      auto cmp = [&](uint64_t x) { return lane_cmp_img2(a.rkeys + a.rkey_off[x], klen(x), kp, kl, khi, klo); };
+      auto cmp_key = [&](uint64_t x) { return lane_cmp_img2(a.rkeys + a.rkey_off[x], klen(x), kp, kl, khi, klo); };
+      // the reader's rule on e and its own run's predecessor
+      auto own_rule = [&](uint64_t read_ts) {
+        bool k = a.rts[e] <= read_ts && a.rval_off[e + 1] > a.rval_off[e];
+        if (k && e > a.sseg[r] && a.rts[e - 1] <= read_ts)
+          k = lane_cmp2(a.rkeys + a.rkey_off[e - 1], klen(e - 1), kp, kl) != 0;
+        return k;
+      };
+      uint64_t ets = 0, snap_ts = 0;
+      bool vis = true;  // kNewest: e passes the reader's rule as far as the runs seen tell
+      if constexpr (kNewest) {
+        ets = a.rts[e];
+        if (a.q_ts) {
+          snap_ts = a.q_ts[q];
+          vis = own_rule(snap_ts);
+        }
+      }
+      auto cmp = [&](uint64_t x) {
+        int c = cmp_key(x);
+        if constexpr (kNewest) {
+          if (c == 0) {
+            const uint64_t tx = a.rts[x];
+            c = tx > ets ? -1 : (tx < ets ? 1 : 0);
+          }
+        }
+        return c;
+      };
       uint64_t pos = e - a.sseg[r];
       owned = true;
       for (uint32_t r2 = r0; r2 < r1; ++r2) {
@@ -1825,20 +1863,21 @@ __global__ __launch_bounds__(256) void lsm_scan_rank_kernel(LsmScanArgs a) {
           }
         }
         pos += p - x0;
-        if (upper && p > x0 && cmp(p - 1) == 0) owned = false;
+        if constexpr (kNewest) {
+          // (a key-only compare: the order above includes ts)
+          if (vis && a.q_ts && p > x0 && cmp_key(p - 1) == 0 && a.rts[p - 1] <= snap_ts) vis = false;
+        } else {
+          if (upper && p > x0 && cmp(p - 1) == 0) owned = false;
+        }
       }
       bool keep = owned;
-      if (keep && a.q_ts) {
-        const uint64_t read_ts = a.q_ts[q];
-        keep = a.rts[e] <= read_ts && a.rval_off[e + 1] > a.rval_off[e];
-        if (keep && e > a.sseg[r] && a.rts[e - 1] <= read_ts)
-          keep = lane_cmp2(a.rkeys + a.rkey_off[e - 1], klen(e - 1), kp, kl) != 0;
-      }
+      if constexpr (kNewest) keep = vis;
+      else if (keep && a.q_ts) keep = own_rule(a.q_ts[q]);
       const uint64_t at = uint64_t(a.sseg[r0]) + pos;
       if (at < nraw) a.slot[at] = keep ? uint32_t(e) + 1 : 0u;
     }
     // merged entries: a tile's lanes are in raw order, so a range's lanes are consecutive; its first
-    // lane adds the range's owned lanes
+    // lane adds the range's owned lanes (kNewest: all of them)
     const uint64_t om = __ballot(on && owned);
     const uint32_t qp = __shfl_up(q, 1, 64);
     const bool head = on && (l == 0 || qp != q);
@@ -2167,7 +2206,9 @@ int lsmblk_lsm_scan_batch(lsmblk_ctx* c, const uint8_t* files, const uint64_t* f
                           const uint32_t* q_bound, const uint64_t* q_ts, uint64_t nq, uint32_t flags, uint64_t sub_cap,
                           lsmblk_lsm_scan_result* res, const lsmblk_kv_stream* raw, const lsmblk_kv_stream* out,
                           uint32_t* seg_start, uint64_t* stats, void* stream) {
-  if (!c || !stats || !seg_start || !view || (flags & ~LSMBLK_SCAN_MVCC) || (out && !raw)) return LSMBLK_E_INVAL;
+  if (!c || !stats || !seg_start || !view || (flags & ~(LSMBLK_SCAN_MVCC | LSMBLK_LSM_SCAN_NEWEST)) || (out && !raw))
+    return LSMBLK_E_INVAL;
+  const bool newest = (flags & LSMBLK_LSM_SCAN_NEWEST) != 0;  // (implies the corrected landing)
   if ((view->nl0 && !view->l0) || (view->nlevel && (!view->level_start || !view->level_sst)) ||
       uint64_t(view->nl0) + view->nlevel >= 0xFFFFFFFFull)
     return LSMBLK_E_INVAL;
@@ -2298,7 +2339,7 @@ int lsmblk_lsm_scan_batch(lsmblk_ctx* c, const uint8_t* files, const uint64_t* f
   s.ukey_off = ukey_off;
   s.q_bound = q_bound;
   s.nq = 0;
-  s.flags = flags | LSMBLK_SCAN_NO_FILTER;
+  s.flags = (newest ? LSMBLK_SCAN_MVCC : flags) | LSMBLK_SCAN_NO_FILTER;
   s.res = reinterpret_cast<lsmblk_scan_result*>(W + o_sres);
   if (raw) {
     s.okeys = raw->keys;
@@ -2335,7 +2376,10 @@ int lsmblk_lsm_scan_batch(lsmblk_ctx* c, const uint8_t* files, const uint64_t* f
   LSM_LAUNCH_NAMED("lsm_scan_expand_fill_kernel", lsm_scan_expand_kernel<true>, grid(nq, kGetWaves), dim3(64 * kGetWaves), 0,
                    st, a);
   launch_scan<true>(s, grid(sub_cap, kGetWaves).x, grid(units, kGetWaves).x, raw != nullptr, st);
-  if (raw) LSM_LAUNCH(lsm_scan_rank_kernel, grid(slot_cap, 256), dim3(256), 0, st, a);
+  if (raw && newest)
+    LSM_LAUNCH_NAMED("lsm_scan_rank_newest_kernel", lsm_scan_rank_kernel<true>, grid(slot_cap, 256), dim3(256), 0, st, a);
+  else if (raw)
+    LSM_LAUNCH_NAMED("lsm_scan_rank_kernel", lsm_scan_rank_kernel<false>, grid(slot_cap, 256), dim3(256), 0, st, a);
   LSM_LAUNCH(lsm_scan_offsets_kernel, dim3(1), dim3(kScanWg), 0, st, a);
   if (out) LSM_LAUNCH(lsm_scan_gather_kernel, grid(slot_cap, 16), dim3(256), 0, st, a);
   return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;

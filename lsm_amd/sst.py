@@ -31,7 +31,7 @@ import torch
 from . import batch
 from ._lib import (LSMBLK_BOUND_EXCLUDED, LSMBLK_BOUND_INCLUDED, LSMBLK_BOUND_UNBOUNDED, LSMBLK_E_CAPACITY,
                    LSMBLK_GET_FOUND, LSMBLK_GET_MVCC, LSMBLK_GET_NO_FILTER, LSMBLK_LSM_GET_NEWEST,
-                   LSMBLK_LSM_SCAN_STATS_WORDS, LSMBLK_SCAN_MVCC, LSMBLK_SCAN_NO_FILTER, GetResultC, LsmBlkError,
+                   LSMBLK_LSM_SCAN_NEWEST, LSMBLK_LSM_SCAN_STATS_WORDS, LSMBLK_SCAN_MVCC, LSMBLK_SCAN_NO_FILTER, GetResultC, LsmBlkError,
                    LsmGetResultC, LsmScanResultC, LsmViewC, ScanResultC, SstDescC, SstIndexC, check, lib)
 
 
@@ -631,20 +631,25 @@ class SstSet:
                 out.n = st[0]
         return r, seg.cpu().numpy().view(np.uint32), raw, out, st
 
-    def lsm_scan(self, view, lower, upper, *, lower_kind, upper_kind, read_ts=None, mvcc=False, sub_cap=None):
+    def lsm_scan(self, view, lower, upper, *, lower_kind, upper_kind, read_ts=None, mvcc=False, sub_cap=None,
+                 newest=False):
         """scan_with_ts below the memtables for a batch of ranges over `view`: range i = (lower[i],
         upper[i]) with the bound kinds, at read_ts[i] (or the scalar read_ts) -> (dict of numpy arrays:
         status, sources, raw, merged, n; and per range the list of (key, ts, value)).  read_ts None:
-        the merged stream, every version of every key's owning table.  sub_cap defaults to every table
+        the merged stream, every version of every key's owning table.  newest
+        (LSMBLK_LSM_SCAN_NEWEST, which implies mvcc): the snapshot scan -- the runs merged by (key
+        ascending, ts descending), so per key the row is the newest version at or below read_ts over
+        every source, as lsm_get(newest=True) gives for one key; with read_ts None the rows are every
+        version of every key from every passing table, in that order.  sub_cap defaults to every table
         of the view for every range, which always fits.  Retries at most once on CAPACITY, relying on
         which stats words the header declares valid: a short sub_cap reports only [7], a short raw
         stream [4..7], a short out stream every word (out never needs more than raw)."""
         nq = len(lower)
         cap = view_sub_cap(view, nq) if sub_cap is None else sub_cap
         rc = oc = (64 * nq + 1024, 1024 * nq + 4096, 4096 * nq + 4096)
+        flags = (LSMBLK_SCAN_MVCC if mvcc else 0) | (LSMBLK_LSM_SCAN_NEWEST if newest else 0)
         for _ in range(2):
-            r, seg, _, kv, st = self.lsm_scan_raw(view, lower, upper, lower_kind, upper_kind, read_ts,
-                                                  LSMBLK_SCAN_MVCC if mvcc else 0, cap, rc, oc)
+            r, seg, _, kv, st = self.lsm_scan_raw(view, lower, upper, lower_kind, upper_kind, read_ts, flags, cap, rc, oc)
             if st[3] != ERR_CAPACITY:
                 break
             if st[7] > cap:  # no scan ran: the streams' sizes are still unknown

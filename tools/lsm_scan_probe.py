@@ -15,12 +15,16 @@ uniformly random n0, read_ts above every ts.  One JSON line to stdout and OUT:
                the run boundaries back, then per range a 16-byte aligned copy of its runs, one
                lsmblk_merge_batch (a round trip to size its output) and one lsmblk_read_filter_batch
   equal        kept entries and key bytes of both routes agree
+  modes        the same batch with LSMBLK_SCAN_MVCC and with LSMBLK_LSM_SCAN_NEWEST (--modes): wall ms per
+               batch and the rank kernel's ms from the kernel log, and newest_over_mvcc, the ratio of both
   rank70       separately: a view of 70 L0 tables of 1 MiB that every range crosses -- 69 searches per
-               raw entry -- and lsm_scan_rank_kernel's ms from the kernel log: entries/s, searches/s
+               raw entry -- and lsm_scan_rank_kernel's ms from the kernel log: entries/s, searches/s; the
+               rank kernel's ms in every mode of --modes
 
 Every timed figure: 1 warm-up run, then RUNS runs; median, min and max.  Every GPU step runs under
 its own time limit (SIGALRM ends the process).
 usage: python tools/lsm_scan_probe.py [OUT_JSON] [--sst-mib M] [--ranges Q] [--span S] [--runs R]
+                                     [--modes mvcc,newest] [--no-composition]
 """
 import argparse
 import ctypes
@@ -41,6 +45,8 @@ from lsm_amd._build import src_sha  # noqa: E402
 from lsm_amd._lib import LSMBLK_LSM_SCAN_STATS_WORDS, LsmScanResultC, ScanResultC, kernel_log, lib  # noqa: E402
 
 INCL_EXCL = 1 | (2 << 2)
+MODE_FLAGS = {"default": 0, "mvcc": 2, "newest": 4}  # LSMBLK_SCAN_MVCC, LSMBLK_LSM_SCAN_NEWEST
+RANK_KERNELS = ("lsm_scan_rank_kernel", "lsm_scan_rank_newest_kernel")
 
 
 def step(name, seconds):
@@ -100,9 +106,9 @@ class Set:
 class LsmScan:
     """The new call over one batch of ranges, into streams sized by two sizing calls."""
 
-    def __init__(self, s, lo_id, hi_id):
+    def __init__(self, s, lo_id, hi_id, flags=0):
         ss, dev, nq = s.ss, s.dev, len(lo_id)
-        self.s, self.nq = s, nq
+        self.s, self.nq, self.flags = s, nq, flags
         self.lk = torch.from_numpy(key_bytes(lo_id).reshape(-1)).to(dev)
         self.uk = torch.from_numpy(key_bytes(hi_id).reshape(-1)).to(dev)
         self.off = batch._u32_table(np.arange(nq + 1, dtype=np.uint64) * KLEN, dev)
@@ -121,7 +127,7 @@ class LsmScan:
         assert self.st[3] == 0, self.st
 
     def run(self):
-        self.s.ss.lsm_scan_into(self.s.view, self.lk, self.off, self.uk, self.off, self.bnd, self.ts, self.nq, 0, self.sub_cap,
+        self.s.ss.lsm_scan_into(self.s.view, self.lk, self.off, self.uk, self.off, self.bnd, self.ts, self.nq, self.flags, self.sub_cap,
                                 self.res, self.seg, self.stats, self.raw, self.out)
 
     def call(self):
@@ -172,6 +178,34 @@ def composition(s, lo_id, hi_id, caps):
     return kept, kbytes
 
 
+def kernel_times(ctx, scan, calls=3):
+    """ms per launch of every kernel of `calls` calls (LSMBLK_DEBUG_KERNEL_TIMING, a pass of its own)."""
+    lib().lsmblk_debug_set(ctx, 2, 1)
+    kernel_log(ctx)
+    for _ in range(calls):
+        scan.call()
+    kern = {k: ms_ / ln for k, (ln, ms_) in kernel_log(ctx).items()}
+    lib().lsmblk_debug_set(ctx, 2, 0)
+    return kern
+
+
+def mode_legs(ctx, s, lo_id, hi_id, modes, runs, want):
+    """Per mode: the batch's wall ms and its rank kernel's ms; the sizes must be `want`'s (one version
+    per key and no key in two tables: every mode keeps every entry)."""
+    out = {}
+    for m in modes:
+        scan = LsmScan(s, lo_id, hi_id, MODE_FLAGS[m])
+        assert scan.st[:3] == want[:3] and scan.st[4:] == want[4:], (m, scan.st, want)
+        ms = wall(scan.run, runs)
+        kern = kernel_times(ctx, scan, 5)
+        out[m] = dict(rank_kernel_ms=round(sum(kern.get(k, 0.0) for k in RANK_KERNELS), 4), **spread(ms))
+        del scan
+    if "mvcc" in out and "newest" in out:
+        out["newest_over_mvcc"] = dict(wall=round(out["newest"]["median_ms"] / out["mvcc"]["median_ms"], 3),
+                                       rank_kernel=round(out["newest"]["rank_kernel_ms"] / out["mvcc"]["rank_kernel_ms"], 3))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("out", nargs="?", default=os.path.join("profiles", "lsm_scan_probe.json"))
@@ -180,7 +214,10 @@ def main():
     ap.add_argument("--span", type=int, default=32)
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--rank-ranges", type=int, default=256)
+    ap.add_argument("--modes", default="mvcc,newest", help="comma list of mvcc, newest (empty: none)")
+    ap.add_argument("--no-composition", action="store_true")
     a = ap.parse_args()
+    modes = [m for m in a.modes.split(",") if m]
     if not torch.cuda.is_available():
         sys.exit("lsm_scan_probe needs a ROCm device")
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -209,15 +246,19 @@ def main():
                             out_bytes=out_bytes, ranges_per_s=round(a.ranges / med * 1e3), out_gb_per_s=round(out_bytes / med / 1e6, 3),
                             kernels_ms_per_launch=kern, **spread(ms))
 
-    step("composition: scan, merge per range, read filter", 900)
-    caps = (st[4], st[5], st[6])
-    kept = composition(s, lo_id, hi_id, caps)
-    cms = wall(lambda: composition(s, lo_id, hi_id, caps), max(1, a.runs // 2))
-    cmed = sorted(cms)[len(cms) // 2]
-    line["composition"] = dict(ranges=a.ranges, kept=kept[0], ranges_per_s=round(a.ranges / cmed * 1e3),
-                               out_gb_per_s=round(out_bytes / cmed / 1e6, 3), **spread(cms))
-    line["equal"] = bool(kept == (st[0], st[1]))
-    line["speedup"] = round(cmed / med, 2)
+    if modes:
+        step("modes: the same batch with " + ", ".join(modes), 300)
+        line["modes"] = mode_legs(ctx, s, lo_id, hi_id, modes, a.runs, st)
+    if not a.no_composition:
+        step("composition: scan, merge per range, read filter", 900)
+        caps = (st[4], st[5], st[6])
+        kept = composition(s, lo_id, hi_id, caps)
+        cms = wall(lambda: composition(s, lo_id, hi_id, caps), max(1, a.runs // 2))
+        cmed = sorted(cms)[len(cms) // 2]
+        line["composition"] = dict(ranges=a.ranges, kept=kept[0], ranges_per_s=round(a.ranges / cmed * 1e3),
+                                   out_gb_per_s=round(out_bytes / cmed / 1e6, 3), **spread(cms))
+        line["equal"] = bool(kept == (st[0], st[1]))
+        line["speedup"] = round(cmed / med, 2)
     del new, s
     torch.cuda.empty_cache()
 
@@ -236,6 +277,9 @@ def main():
     line["rank70"] = dict(ranges=a.rank_ranges, runs_per_range=70, raw_entries=raw, rank_kernel_ms=round(rk, 4),
                           entries_per_s=round(raw / rk * 1e3), searches_per_s=round(raw * 69 / rk * 1e3),
                           all_kernels_ms={k: round(v, 4) for k, v in kern.items()})
+    if modes:
+        step("rank70: modes", 300)
+        line["rank70"]["modes"] = mode_legs(ctx, s, lo_id, hi_id, modes, a.runs, new.st)
     signal.alarm(0)
     print(json.dumps(line), flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
