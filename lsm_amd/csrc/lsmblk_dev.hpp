@@ -511,6 +511,55 @@ struct GlbImg {
   }
 };
 
+// ---------------------------------------------------------------- the block parser
+// The one definition of a well-formed block ("Validation rules"): the decode, its counts,
+// crc_kernel<true>'s count_block and the scan kernels of lsmblk_get.hip parse through these two
+// functions, and every read kernel takes its header from parse_hdr, so they give one MALFORMED
+// verdict.  Two restatements of the entry rules remain, each load behind its check: seek_kernel
+// (lsmblk_sst.hip: a raw pointer, a load must not leave the block) and block_lu (lsmblk_get.hip:
+// the point read measured slower through parse_entry).  tests/test_gpu_block_rules.py holds all of
+// them to every rule.
+// Contract: parse_entry loads before it checks, so the image's out-of-range reads must not fault --
+// GlbImg's descriptor returns 0 past its bound, an LDS read past the image returns other LDS bytes
+// or 0 -- and whatever such a read returns, the entry fails a rule.  A failed entry's p, s and vl
+// are 0.
+struct BlockHdr {
+  uint32_t len, n, data_end, fks;
+  bool ok;
+};
+
+template <class Img>
+__device__ __forceinline__ BlockHdr parse_hdr(const Img& im, uint32_t len) {
+  BlockHdr h{len, 0, 0, 0, true};
+  if (len < 2) { h.ok = false; return h; }
+  h.n = im.u16(len - 2);
+  if (2 + 2 * h.n > len) { h.ok = false; h.n = 0; return h; }
+  h.data_end = len - 2 - 2 * h.n;
+  if (h.n) {
+    // get_first_key (iterator.rs:23-34) parses the entry at data position 0.
+    if (h.data_end < 4) { h.ok = false; return h; }
+    h.fks = im.u16(2);
+    if (4 + h.fks + 8 > h.data_end) h.ok = false;
+  }
+  return h;
+}
+
+// Corrected seek_to_offset (iterator.rs:125-139) with the validation rules of DESIGN.md.
+template <class Img>
+__device__ __forceinline__ bool parse_entry(const Img& im, const BlockHdr& h, uint32_t k,
+                                            uint32_t& off, uint32_t& p, uint32_t& s, uint32_t& vl) {
+  off = im.u16(h.data_end + 2 * k);
+  bool ok = off + 4 <= h.data_end;
+  const uint32_t w = im.le32(off);  // BE16 p | BE16 s
+  p = bswap16(w & 0xFFFF);
+  s = bswap16(w >> 16);
+  ok = ok && (off + 4 + s + 10 <= h.data_end) && (p <= h.fks) && (p + s > 0);
+  vl = im.u16(off + 12 + s);
+  ok = ok && (off + 14 + s + vl <= h.data_end);
+  if (!ok) { p = s = vl = 0; }
+  return ok;
+}
+
 // 4 bytes starting at byte offset x of a 4-byte-aligned LDS buffer.
 __device__ __forceinline__ uint32_t lds_dword_at(const uint8_t* base, uint32_t x) {
   return *reinterpret_cast<const uint32_t*>(base + x);  // unaligned ds_read_b32
@@ -981,6 +1030,13 @@ struct DeviceGuard {
   DeviceGuard(const DeviceGuard&) = delete;
   DeviceGuard& operator=(const DeviceGuard&) = delete;
 };
+
+// The compute units of the context's device, as the runtime reports them (256 when it cannot say).
+inline int cu_count(const lsmblk_ctx* c) {
+  int cus = 256;
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
+  return cus;
+}
 
 // The next kernel-log entry of c (events created on first use of a ring slot), nullptr when
 // events cannot be created (the launch then runs untimed).

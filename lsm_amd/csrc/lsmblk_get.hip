@@ -258,24 +258,58 @@ __global__ __launch_bounds__(64) void sst_open_walk_kernel(OpenArgs a) {
   }
 }
 
-// ---------------------------------------------------------------- get
-struct GetArgs {
+// ---------------------------------------------------------------- the read calls' arguments
+// The pieces the kernel argument structs of the four read calls are composed of: each field list is
+// written here once.  A base struct's fields keep their spelling in the kernels (a.files, a.nl0).
+struct OpenedSet {  // what lsmblk_sst_open_batch made of the resident files
   const uint8_t* files;
   const uint64_t* file_off;
   uint32_t nsst;
   const lsmblk_sst_desc* desc;
   const lsmblk_sst_index* index;
-  const uint32_t* q_sst;
+};
+struct ViewArgs {  // lsmblk_lsm_view
+  const uint32_t* l0;
+  uint32_t nl0, nlevel;
+  const uint32_t* level_sst;
+  const uint32_t* level_start;
+};
+struct PointArgs {  // a batch of point reads and where their values go
   const uint8_t* qkeys;
   const uint32_t* qkey_off;
   const uint64_t* q_ts;
   uint64_t nq;
   uint32_t flags;
-  lsmblk_get_result* res;
   uint8_t* vals;
   uint64_t val_cap;
   uint32_t* val_off;
   uint64_t* stats;
+};
+struct BoundArgs {  // a batch of ranges: bound keys and kinds
+  const uint8_t* lkeys;
+  const uint32_t* lkey_off;
+  const uint8_t* ukeys;
+  const uint32_t* ukey_off;
+  const uint32_t* q_bound;
+};
+struct DevStream {  // a lsmblk_kv_stream the kernels write (or read back); on: the caller gave one
+  uint8_t* keys;
+  uint32_t* key_off;
+  uint8_t* vals;
+  uint32_t* val_off;
+  uint64_t* ts;
+  uint64_t entry_cap, key_cap, val_cap;
+  uint32_t on;
+};
+DevStream dev_stream(const lsmblk_kv_stream* s) {
+  if (!s) return DevStream{};
+  return DevStream{s->keys, s->key_off, s->vals, s->val_off, s->ts, s->entry_cap, s->key_cap, s->val_cap, 1u};
+}
+
+// ---------------------------------------------------------------- get
+struct GetArgs : OpenedSet, PointArgs {
+  const uint32_t* q_sst;
+  lsmblk_get_result* res;
 };
 
 // The query key through a bounds-checked descriptor over the arena up to the key's end (rounded up
@@ -392,24 +426,14 @@ __device__ __forceinline__ uint32_t index_partition(const lsmblk_sst_index* ix, 
   return P;
 }
 
-struct BlkHdr {
-  uint32_t n, data_end, fks;
-  bool ok;
-};
-// Block::decode's header with seek_kernel's checks (lsmblk_sst.hip).
+// The shared parse_hdr (lsmblk_dev.hpp) for a wave that reads one block: every lane loads the same
+// header, so its fields are made wave-uniform.
 template <class Img>
-__device__ __forceinline__ BlkHdr get_hdr(const Img& im, uint32_t len) {
-  BlkHdr h{0, 0, 0, false};
-  if (len < 2) return h;
-  h.n = uni(im.u16(len - 2));
-  if (2 + 2 * h.n > len) return h;
-  h.data_end = len - 2 - 2 * h.n;
-  if (h.n) {
-    if (h.data_end < 4) return h;
-    h.fks = uni(im.u16(2));
-    if (4 + h.fks + 8 > h.data_end) return h;
-  }
-  h.ok = true;
+__device__ __forceinline__ BlockHdr get_hdr(const Img& im, uint32_t len) {
+  BlockHdr h = parse_hdr(im, len);
+  h.n = uni(h.n);
+  h.data_end = uni(h.data_end);
+  h.fks = uni(h.fks);
   return h;
 }
 
@@ -417,7 +441,7 @@ __device__ __forceinline__ BlkHdr get_hdr(const Img& im, uint32_t len) {
 // entries not above it, so [L, U) is the equal range (the block is sorted).  Every entry is parsed
 // and checked; false: the block breaks the decode rules.
 template <class Img>
-__device__ __forceinline__ bool block_lu(const Img& im, const BlkHdr& h, const QKey& q, uint32_t& L, uint32_t& U) {
+__device__ __forceinline__ bool block_lu(const Img& im, const BlockHdr& h, const QKey& q, uint32_t& L, uint32_t& U) {
   const uint32_t l = lane_id();
   // m = lcp(first key, query); an entry that shares more than m bytes with the first key orders
   // against the query as the first key does at byte m, one that shares at most m has its first
@@ -433,6 +457,9 @@ __device__ __forceinline__ bool block_lu(const Img& im, const BlkHdr& h, const Q
     const uint32_t e = c + l;
     int cm = 1;
     if (e < h.n) {
+      // parse_entry's rules (lsmblk_dev.hpp), every load behind its check as in seek_kernel: through
+      // the shared load-then-check form a filtered lsmblk_sst_get_batch measured 3.8 % slower
+      // ("One block parser ..."); tests/test_gpu_block_rules.py holds this copy to the rules
       const uint32_t off = im.u16(h.data_end + 2 * e);
       bool okk = off + 4 <= h.data_end;
       uint32_t pf = 0, sf = 0;
@@ -486,7 +513,7 @@ template <class Img>
 __device__ Visit visit_block(const Img& im, uint32_t len, uint64_t bpos, uint32_t b, bool first, bool mvcc,
                              const QKey& q, uint64_t read_ts, Look& k) {
   const uint32_t l = lane_id();
-  const BlkHdr h = get_hdr(im, len);
+  const BlockHdr h = get_hdr(im, len);
   if (!h.ok) return Visit{true, true};
   uint32_t L = 0, U = 0;
   if (!block_lu(im, h, q, L, U)) return Visit{true, true};
@@ -552,14 +579,6 @@ __device__ Visit visit_block(const Img& im, uint32_t len, uint64_t bpos, uint32_
   return Visit{U < h.n, false};
 }
 
-// The opened set a lookup reads.
-struct Opened {
-  const uint8_t* files;
-  const uint64_t* file_off;
-  const lsmblk_sst_desc* desc;
-  const lsmblk_sst_index* index;
-};
-
 struct QHash {  // fingerprint32 of the query key, computed by the first bloom test that needs it
   uint32_t h;
   bool valid;
@@ -568,7 +587,7 @@ struct QHash {  // fingerprint32 of the query key, computed by the first bloom t
 // One table's read of one key (wave-uniform): key_within, the bloom test, find_block_idx, the landed
 // block and the blocks the iterator moves on to -> k (k.status also RANGE_OUT / BLOOM_OUT; k.on_key:
 // the landing entry's key is the query).  True: a block on the path breaks the decode rules.
-__device__ __forceinline__ bool sst_lookup(const Opened& o, uint32_t s, const QKey& q, uint64_t read_ts, bool mvcc,
+__device__ __forceinline__ bool sst_lookup(const OpenedSet& o, uint32_t s, const QKey& q, uint64_t read_ts, bool mvcc,
                                            bool filter, uint8_t* S, QHash& qh, Look& k) {
   const uint32_t l = lane_id();
   const lsmblk_sst_desc* dp = o.desc + s;
@@ -678,7 +697,7 @@ __global__ __launch_bounds__(64 * kGetWaves) __attribute__((amdgpu_waves_per_eu(
   const bool mvcc = (a.flags & LSMBLK_GET_MVCC) != 0, filter = !(a.flags & LSMBLK_GET_NO_FILTER);
   const uint32_t qlead = uint32_t(reinterpret_cast<uintptr_t>(a.qkeys) & 3);
   const uint8_t* const qbase = a.qkeys - qlead;
-  const Opened o{a.files, a.file_off, a.desc, a.index};
+  const OpenedSet& o = a;
   uint32_t err = 0, nfound = 0;
   if (blockIdx.x == 0 && threadIdx.x == 0) a.stats[0] = a.nq;
   const uint64_t stride = uint64_t(gridDim.x) * kGetWaves;
@@ -719,27 +738,13 @@ __global__ __launch_bounds__(64 * kGetWaves) __attribute__((amdgpu_waves_per_eu(
 
 // ---------------------------------------------------------------- the LSM point read
 // lsmblk_lsm_get_batch: the view check, then one wave per key over the view's sources.
-struct LsmGetArgs {
-  const uint8_t* files;
-  const uint64_t* file_off;
-  uint32_t nsst;
-  const lsmblk_sst_desc* desc;
-  const lsmblk_sst_index* index;
-  const uint32_t* l0;
-  uint32_t nl0, nlevel;
-  const uint32_t* level_sst;
-  const uint32_t* level_start;
-  const uint8_t* qkeys;
-  const uint32_t* qkey_off;
-  const uint64_t* q_ts;
-  uint64_t nq;
-  uint32_t flags;
-  lsmblk_lsm_get_result* res;
-  uint8_t* vals;
-  uint64_t val_cap;
-  uint32_t* val_off;
+struct ViewCheckArgs : OpenedSet, ViewArgs {
   uint64_t* stats;
-  uint32_t* vflag;  // the view check's verdict (workspace): error flags, 0 = the lookups run
+  uint32_t* vflag;  // the view check's verdict (workspace): error flags, 0 = the reads run
+};
+struct LsmGetArgs : OpenedSet, ViewArgs, PointArgs {
+  lsmblk_lsm_get_result* res;
+  uint32_t* vflag;
 };
 
 // key order of file bytes a[0 .. la) against b[0 .. lb) by one lane
@@ -754,7 +759,7 @@ __device__ int lane_cmp2(const uint8_t* x, uint32_t la, const uint8_t* y, uint32
 // level_start first, by every workgroup -- it bounds the reads of level_sst -- then per entry the id,
 // its open, and for a level entry with a right neighbour check_sst_valid's order
 // (concat_iterator.rs:82-93), last_key(i) < first_key(i + 1), through the descriptors' key positions.
-__global__ __launch_bounds__(256) void lsm_view_check_kernel(LsmGetArgs a) {
+__global__ __launch_bounds__(256) void lsm_view_check_kernel(ViewCheckArgs a) {
   int sb = 0;
   for (uint32_t i = threadIdx.x; i < a.nlevel; i += 256)
     sb |= (i == 0 && a.level_start[0] != 0) || a.level_start[i + 1] < a.level_start[i];
@@ -803,14 +808,14 @@ __global__ __launch_bounds__(256) void lsm_view_check_kernel(LsmGetArgs a) {
 // first_key <= q, counted as index_partition counts blocks -- a table's first key is its first
 // block's, so index[desc[t].blk0] holds its image; whole keys only inside the image tie range.
 // Table t's image against the query's: 1 = below it, 2 = not above it.
-__device__ __forceinline__ uint32_t table_img_le(const Opened& o, uint32_t nsst, uint32_t t, uint64_t qhi, uint64_t qlo) {
+__device__ __forceinline__ uint32_t table_img_le(const OpenedSet& o, uint32_t nsst, uint32_t t, uint64_t qhi, uint64_t qlo) {
   if (t >= nsst) return 0;  // (the view check refuses such a view)
   const u32x4 v = *reinterpret_cast<const u32x4*>(o.index + o.desc[t].blk0);
   const uint64_t hi = (uint64_t(v.y) << 32) | v.x, lo = (uint64_t(v.w) << 32) | v.z;
   return (hi < qhi || (hi == qhi && lo < qlo) ? 1u : 0u) | (hi < qhi || (hi == qhi && lo <= qlo) ? 2u : 0u);
 }
 // ... and the partition point from the image bounds: whole keys inside [iL, iU)
-__device__ __forceinline__ uint32_t level_tie(const Opened& o, uint32_t nsst, const uint32_t* ls, uint32_t iL, uint32_t iU,
+__device__ __forceinline__ uint32_t level_tie(const OpenedSet& o, uint32_t nsst, const uint32_t* ls, uint32_t iL, uint32_t iU,
                                               const QKey& q) {
   if (iU <= iL) return iL;
   return kary_first_false(iL, iU, [&](uint32_t i) {
@@ -819,7 +824,7 @@ __device__ __forceinline__ uint32_t level_tie(const Opened& o, uint32_t nsst, co
     return lane_cmp(o.files + o.desc[t].first_key_pos, o.desc[t].first_key_len, q) <= 0;
   });
 }
-__device__ __forceinline__ uint32_t level_partition(const Opened& o, uint32_t nsst, const uint32_t* ls, uint32_t n,
+__device__ __forceinline__ uint32_t level_partition(const OpenedSet& o, uint32_t nsst, const uint32_t* ls, uint32_t n,
                                                     const QKey& q, uint64_t qhi, uint64_t qlo) {
   const uint32_t iL = kary_first_false(0, n, [&](uint32_t i) { return (table_img_le(o, nsst, ls[i], qhi, qlo) & 1) != 0; });
   const uint32_t iU = kary_first_false(iL, n, [&](uint32_t i) { return (table_img_le(o, nsst, ls[i], qhi, qlo) & 2) != 0; });
@@ -843,14 +848,14 @@ __device__ __forceinline__ int lane_cmp_img(const uint8_t* p, uint32_t len, cons
 
 // keep_table (lsm_storage.rs:383-398) by one lane for its own table, in two steps so that the key
 // is hashed only when some table's range holds it: key_within ...
-__device__ __forceinline__ bool lane_key_within(const Opened& o, uint32_t t, const QKey& q, uint64_t qhi, uint64_t qlo) {
+__device__ __forceinline__ bool lane_key_within(const OpenedSet& o, uint32_t t, const QKey& q, uint64_t qhi, uint64_t qlo) {
   const lsmblk_sst_desc* d = o.desc + t;
   if (d->nblk == 0) return false;  // not opened (the view check refuses such a view)
   return lane_cmp_img(o.files + d->first_key_pos, d->first_key_len, q, qhi, qlo) <= 0 &&
          lane_cmp_img(o.files + d->last_key_pos, d->last_key_len, q, qhi, qlo) >= 0;
 }
 // ... and Bloom::may_contain (bloom.rs:104-120), every probe made (independent loads)
-__device__ __forceinline__ bool lane_may_contain(const Opened& o, uint32_t t, uint32_t h) {
+__device__ __forceinline__ bool lane_may_contain(const OpenedSet& o, uint32_t t, uint32_t h) {
   const lsmblk_sst_desc* d = o.desc + t;
   const uint32_t bk = d->bloom_k, nbits = d->bloom_len * 8u;
   if (bk > 30) return true;
@@ -885,7 +890,7 @@ __global__ __launch_bounds__(64 * kGetWaves) __attribute__((amdgpu_waves_per_eu(
   const bool newest = (a.flags & LSMBLK_LSM_GET_NEWEST) != 0, mvcc = newest || (a.flags & LSMBLK_GET_MVCC) != 0;
   const uint32_t qlead = uint32_t(reinterpret_cast<uintptr_t>(a.qkeys) & 3);
   const uint8_t* const qbase = a.qkeys - qlead;
-  const Opened o{a.files, a.file_off, a.desc, a.index};
+  const OpenedSet& o = a;
   const bool run = uni(*a.vflag) == 0;
   const uint32_t nsrc = a.nl0 + a.nlevel;
   const uint32_t nlv = run && a.nlevel ? uni(a.level_start[a.nlevel]) : 0u;  // level tables in all
@@ -1045,35 +1050,20 @@ __global__ __launch_bounds__(256) void val_gather_kernel(Args a) {
 //                        and value of four entries at a time copied in 16-B pieces by 16 lanes each
 constexpr uint32_t kScanWg = 1024;  // threads of the two one-workgroup scans: each takes a contiguous share
 
-struct ScanArgs {
-  const uint8_t* files;
-  const uint64_t* file_off;
-  uint32_t nsst;
-  const lsmblk_sst_desc* desc;
-  const lsmblk_sst_index* index;
+struct ScanArgs : OpenedSet, BoundArgs {
   const uint32_t* q_sst;
-  const uint8_t* lkeys;
-  const uint32_t* lkey_off;
-  const uint8_t* ukeys;
-  const uint32_t* ukey_off;
-  const uint32_t* q_bound;
   uint64_t nq;
   uint32_t flags;
   lsmblk_scan_result* res;
-  uint8_t* okeys;
-  uint32_t* okey_off;
-  uint8_t* ovals;
-  uint32_t* oval_off;
-  uint64_t* ots;
-  uint64_t entry_cap, key_cap, val_cap;
-  uint32_t has_out;
+  DevStream out;
   uint32_t* seg_start;
+  uint64_t* stats;
+  // workspace
   uint32_t* ubase;   // nq + 1: first unit of every range
   uint32_t* qbad;    // nq: a block of the range is malformed
   uint64_t* hdr;     // [0] units, [1] blocks per unit
   uint64_t* ucnt;    // 3 per unit: counts, then their exclusive prefixes
   uint32_t budget;
-  uint64_t* stats;
   // lsmblk_lsm_scan_batch's table scans (the kernels' kSub form): their count, known on the device
   // only, and per scan the range whose bound keys and kinds it takes; q_sst, res, qbad and seg_start
   // are per scan
@@ -1116,24 +1106,11 @@ __device__ __forceinline__ bool on_block(const uint8_t* F, const lsmblk_sst_inde
   return fn(GlbImg{R, lead}, len);
 }
 
-// Entry e of a block by the decode's rules -> its offset, prefix, suffix and value lengths.
-template <class Img>
-__device__ __forceinline__ bool parse_entry(const Img& im, const BlkHdr& h, uint32_t e, uint32_t& off, uint32_t& pf,
-                                            uint32_t& sf, uint32_t& vl) {
-  off = im.u16(h.data_end + 2 * e);
-  if (off + 4 > h.data_end) return false;
-  pf = im.u16(off);
-  sf = im.u16(off + 2);
-  if (!(off + 4 + sf + 10 <= h.data_end && pf <= h.fks && pf + sf > 0)) return false;
-  vl = im.u16(off + 12 + sf);
-  return off + 14 + sf + vl <= h.data_end;
-}
-
 // (entries below the key, entries not above it, entries) of block b; false: malformed
 __device__ __forceinline__ bool scan_lu(const uint8_t* F, const lsmblk_sst_index* ix, uint32_t b, uint32_t meta_offset,
                                         uint8_t* S, const QKey& q, uint32_t& L, uint32_t& U, uint32_t& n) {
   return on_block(F, ix, b, meta_offset, S, [&](const auto& im, uint32_t len) {
-    const BlkHdr h = get_hdr(im, len);
+    const BlockHdr h = get_hdr(im, len);
     if (!h.ok) return false;
     n = h.n;
     return block_lu(im, h, q, L, U);
@@ -1344,7 +1321,7 @@ __device__ __forceinline__ bool unit_blocks(const ScanArgs& a, uint32_t q, uint3
     const uint32_t b = b0 + uint32_t(j);
     if (b >= nblk) return false;
     const bool ok = on_block(F, ix, b, mo, S, [&](const auto& im, uint32_t len) {
-      const BlkHdr h = get_hdr(im, len);
+      const BlockHdr h = get_hdr(im, len);
       if (!h.ok) return false;
       const uint32_t w0 = b == b0 ? e0 : 0u, w1 = b == b1 ? e1 : h.n;
       return fn(im, h, w0, w1 < h.n ? w1 : h.n);
@@ -1364,7 +1341,7 @@ __global__ __launch_bounds__(64 * kGetWaves) void scan_count_kernel(ScanArgs a) 
   for (uint64_t u = uint64_t(blockIdx.x) * kGetWaves + wave_id(); u < nu; u += stride) {
     const uint32_t q = unit_query(a.ubase, nq, uint32_t(u));
     uint64_t ne = 0, kb = 0, vb = 0;
-    const bool ok = unit_blocks(a, q, uint32_t(u), S, [&](const auto& im, const BlkHdr& h, uint32_t w0, uint32_t w1) {
+    const bool ok = unit_blocks(a, q, uint32_t(u), S, [&](const auto& im, const BlockHdr& h, uint32_t w0, uint32_t w1) {
       bool bad = false;
       for (uint32_t c = 0; c < h.n; c += 64) {  // every entry is checked, the window's are counted
         const uint32_t e = c + l;
@@ -1451,8 +1428,8 @@ __global__ __launch_bounds__(kScanWg) void scan_offsets_kernel(ScanArgs a) {
   if (threadIdx.x == 0) {
     // the entry total is held to 2^32 as well (seg_start holds u32 positions in it); a counting
     // call (no outputs) has no caps and no sentinels
-    const TotalCaps caps = a.has_out ? TotalCaps{a.entry_cap, a.key_cap, a.val_cap} : TotalCaps{~0ull, ~0ull, ~0ull};
-    publish_totals(a.stats, tot, caps, a.has_out ? a.okey_off : nullptr, a.has_out ? a.oval_off : nullptr, kSentIfClean, 0,
+    const TotalCaps caps = a.out.on ? TotalCaps{a.out.entry_cap, a.out.key_cap, a.out.val_cap} : TotalCaps{~0ull, ~0ull, ~0ull};
+    publish_totals(a.stats, tot, caps, a.out.on ? a.out.key_off : nullptr, a.out.on ? a.out.val_off : nullptr, kSentIfClean, 0,
                    /*ovf_entries=*/true);
   }
   __threadfence_block();
@@ -1502,7 +1479,7 @@ __global__ __launch_bounds__(64 * kGetWaves) void scan_emit_kernel(ScanArgs a) {
     const uint32_t q = unit_query(a.ubase, nq, uint32_t(u));
     if (uni(a.qbad[q])) continue;
     uint64_t ei = uni64(a.ucnt[3 * u]), ko = uni64(a.ucnt[3 * u + 1]), vo = uni64(a.ucnt[3 * u + 2]);
-    (void)unit_blocks(a, q, uint32_t(u), S, [&](const auto& im, const BlkHdr& h, uint32_t w0, uint32_t w1) {
+    (void)unit_blocks(a, q, uint32_t(u), S, [&](const auto& im, const BlockHdr& h, uint32_t w0, uint32_t w1) {
       for (uint32_t c = w0; c < w1; c += 64) {
         const uint32_t e = c + l, cnt = w1 - c < 64 ? w1 - c : 64u;
         uint32_t off = 0, pf = 0, sf = 0, vl = 0;
@@ -1513,11 +1490,11 @@ __global__ __launch_bounds__(64 * kGetWaves) void scan_emit_kernel(ScanArgs a) {
         const uint64_t mk = ko + ik - kl, mv = vo + iv - vl;  // this entry's key / value place
         // (the totals passed the capacity check; a place past a capacity would be a block that
         // changed since the count: such an entry is not written)
-        live = live && ei + l < a.entry_cap && mk + kl <= a.key_cap && mv + vl <= a.val_cap;
+        live = live && ei + l < a.out.entry_cap && mk + kl <= a.out.key_cap && mv + vl <= a.out.val_cap;
         if (live) {
-          a.okey_off[ei + l] = uint32_t(mk);
-          a.oval_off[ei + l] = uint32_t(mv);
-          a.ots[ei + l] = im.u64(off + 4 + sf);
+          a.out.key_off[ei + l] = uint32_t(mk);
+          a.out.val_off[ei + l] = uint32_t(mv);
+          a.out.ts[ei + l] = im.u64(off + 4 + sf);
         }
         for (uint32_t r = 0; r < cnt; r += 4) {  // four entries a round, 16 lanes each
           const uint32_t t = r + grp;
@@ -1526,9 +1503,9 @@ __global__ __launch_bounds__(64 * kGetWaves) void scan_emit_kernel(ScanArgs a) {
           const uint32_t xvl = __shfl(vl, t, 64);
           const uint32_t xk = __shfl(uint32_t(mk), t, 64), xv = __shfl(uint32_t(mv), t, 64);
           if (on) {
-            quarter_copy(a.okeys + xk, im, 4, xpf, sub);  // first_key[..prefix]
-            quarter_copy(a.okeys + xk + xpf, im, xoff + 4, xsf, sub);
-            quarter_copy(a.ovals + xv, im, xoff + 14 + xsf, xvl, sub);
+            quarter_copy(a.out.keys + xk, im, 4, xpf, sub);  // first_key[..prefix]
+            quarter_copy(a.out.keys + xk + xpf, im, xoff + 4, xsf, sub);
+            quarter_copy(a.out.vals + xv, im, xoff + 14 + xsf, xvl, sub);
           }
         }
         ei += cnt;
@@ -1574,34 +1551,12 @@ void launch_scan(const ScanArgs& a, uint32_t qgrid, uint32_t ugrid, bool emit, h
 //   lsm_scan_offsets_kernel   one workgroup: the three-component scan over the slots in merged order,
 //                             totals, capacity / overflow, key_off / val_off, seg_start, res
 //   lsm_scan_gather_kernel    16 lanes per kept entry: key, value, ts -> out
-struct LsmScanArgs {
-  const uint8_t* files;
-  const lsmblk_sst_desc* desc;
-  uint32_t nsst;
-  const uint32_t* l0;
-  uint32_t nl0, nlevel;
-  const uint32_t* level_sst;
-  const uint32_t* level_start;
-  const uint8_t* lkeys;
-  const uint32_t* lkey_off;
-  const uint8_t* ukeys;
-  const uint32_t* ukey_off;
-  const uint32_t* q_bound;
+struct LsmScanArgs : OpenedSet, ViewArgs, BoundArgs {
   const uint64_t* q_ts;  // null: the merged stream itself
   uint64_t nq, sub_cap;
   lsmblk_lsm_scan_result* res;
-  const uint8_t* rkeys;  // the raw stream (read by the merge)
-  const uint32_t* rkey_off;
-  const uint32_t* rval_off;
-  const uint8_t* rvals;
-  const uint64_t* rts;
-  uint32_t has_raw, has_out;
-  uint8_t* okeys;
-  uint32_t* okey_off;
-  uint8_t* ovals;
-  uint32_t* oval_off;
-  uint64_t* ots;
-  uint64_t entry_cap, key_cap, val_cap;
+  DevStream raw;  // the table scans' output, read by the merge
+  DevStream out;
   uint32_t* seg_start;
   uint64_t* stats;
   // workspace
@@ -1784,7 +1739,7 @@ __global__ __launch_bounds__(256) void lsm_scan_rank_kernel(LsmScanArgs a) {
   if (nraw > a.slot_cap) return;  // (a raw stream that passed its capacity check fits the slots)
   const uint32_t l = lane_id();
   const uint64_t tiles = (nraw + 63) / 64, stride = uint64_t(gridDim.x) * 4;
-  auto klen = [&](uint64_t x) { return a.rkey_off[x + 1] - a.rkey_off[x]; };
+  auto klen = [&](uint64_t x) { return a.raw.key_off[x + 1] - a.raw.key_off[x]; };
   for (uint64_t tile = uint64_t(blockIdx.x) * 4 + wave_id(); tile < tiles; tile += stride) {
     const uint64_t e = tile * 64 + l;
     const bool on = e < nraw;
@@ -1800,7 +1755,7 @@ __global__ __launch_bounds__(256) void lsm_scan_rank_kernel(LsmScanArgs a) {
       const uint32_t r = uint32_t(lo);
       q = a.sub_q[r];
       const uint32_t r0 = a.sbase[q], r1 = a.sbase[q + 1];
-      const uint8_t* const kp = a.rkeys + a.rkey_off[e];
+      const uint8_t* const kp = a.raw.keys + a.raw.key_off[e];
       const uint32_t kl = klen(e);
       uint64_t khi = 0, klo = 0;
 #pragma unroll
@@ -1809,18 +1764,18 @@ __global__ __launch_bounds__(256) void lsm_scan_rank_kernel(LsmScanArgs a) {
         if (j < 8) khi |= b << (56 - 8 * j);
         else klo |= b << (56 - 8 * (j - 8));
       }
-      auto cmp_key = [&](uint64_t x) { return lane_cmp_img2(a.rkeys + a.rkey_off[x], klen(x), kp, kl, khi, klo); };
+      auto cmp_key = [&](uint64_t x) { return lane_cmp_img2(a.raw.keys + a.raw.key_off[x], klen(x), kp, kl, khi, klo); };
       // the reader's rule on e and its own run's predecessor
       auto own_rule = [&](uint64_t read_ts) {
-        bool k = a.rts[e] <= read_ts && a.rval_off[e + 1] > a.rval_off[e];
-        if (k && e > a.sseg[r] && a.rts[e - 1] <= read_ts)
-          k = lane_cmp2(a.rkeys + a.rkey_off[e - 1], klen(e - 1), kp, kl) != 0;
+        bool k = a.raw.ts[e] <= read_ts && a.raw.val_off[e + 1] > a.raw.val_off[e];
+        if (k && e > a.sseg[r] && a.raw.ts[e - 1] <= read_ts)
+          k = lane_cmp2(a.raw.keys + a.raw.key_off[e - 1], klen(e - 1), kp, kl) != 0;
         return k;
       };
       uint64_t ets = 0, snap_ts = 0;
       bool vis = true;  // kNewest: e passes the reader's rule as far as the runs seen tell
       if constexpr (kNewest) {
-        ets = a.rts[e];
+        ets = a.raw.ts[e];
         if (a.q_ts) {
           snap_ts = a.q_ts[q];
           vis = own_rule(snap_ts);
@@ -1830,7 +1785,7 @@ __global__ __launch_bounds__(256) void lsm_scan_rank_kernel(LsmScanArgs a) {
         int c = cmp_key(x);
         if constexpr (kNewest) {
           if (c == 0) {
-            const uint64_t tx = a.rts[x];
+            const uint64_t tx = a.raw.ts[x];
             c = tx > ets ? -1 : (tx < ets ? 1 : 0);
           }
         }
@@ -1865,7 +1820,7 @@ __global__ __launch_bounds__(256) void lsm_scan_rank_kernel(LsmScanArgs a) {
         pos += p - x0;
         if constexpr (kNewest) {
           // (a key-only compare: the order above includes ts)
-          if (vis && a.q_ts && p > x0 && cmp_key(p - 1) == 0 && a.rts[p - 1] <= snap_ts) vis = false;
+          if (vis && a.q_ts && p > x0 && cmp_key(p - 1) == 0 && a.raw.ts[p - 1] <= snap_ts) vis = false;
         } else {
           if (upper && p > x0 && cmp(p - 1) == 0) owned = false;
         }
@@ -1901,7 +1856,7 @@ __global__ __launch_bounds__(kScanWg) void lsm_scan_offsets_kernel(LsmScanArgs a
   const uint32_t serr = uint32_t(a.sstats[3]);
   const uint64_t nraw = nsub ? a.sseg[nsub] : 0;
   // ranked: the raw stream was written and lsm_scan_rank_kernel ran over it
-  const bool ranked = nsub && a.has_raw && !(serr & (LSMBLK_ERR_CAPACITY | LSMBLK_ERR_OVERFLOW)) && nraw <= a.slot_cap;
+  const bool ranked = nsub && a.raw.on && !(serr & (LSMBLK_ERR_CAPACITY | LSMBLK_ERR_OVERFLOW)) && nraw <= a.slot_cap;
   const bool masked = (serr & LSMBLK_ERR_MALFORMED) != 0;
   if (masked)
     for (uint64_t s = threadIdx.x; s < nsub; s += kScanWg)
@@ -1933,30 +1888,30 @@ __global__ __launch_bounds__(kScanWg) void lsm_scan_offsets_kernel(LsmScanArgs a
     if (s != a.slot[i]) a.slot[i] = s;
     if (s) {
       sum[0] += 1;
-      sum[1] += a.rkey_off[s] - a.rkey_off[s - 1];
-      sum[2] += a.rval_off[s] - a.rval_off[s - 1];
+      sum[1] += a.raw.key_off[s] - a.raw.key_off[s - 1];
+      sum[2] += a.raw.val_off[s] - a.raw.val_off[s - 1];
     }
   }
   block_excl1024<3>(sum, wsum, base, tot);
-  const bool fits = a.has_out && tot[0] <= a.entry_cap && tot[1] <= a.key_cap && tot[2] <= a.val_cap &&
+  const bool fits = a.out.on && tot[0] <= a.out.entry_cap && tot[1] <= a.out.key_cap && tot[2] <= a.out.val_cap &&
                     tot[0] <= 0xFFFFFFFFull && tot[1] <= 0xFFFFFFFFull && tot[2] <= 0xFFFFFFFFull;
   for (uint64_t i = i0; i < i1; ++i) {
     const uint32_t s = a.slot[i];
     a.opre[i] = uint32_t(base[0]);
     if (s) {
       if (fits) {
-        a.okey_off[base[0]] = uint32_t(base[1]);
-        a.oval_off[base[0]] = uint32_t(base[2]);
+        a.out.key_off[base[0]] = uint32_t(base[1]);
+        a.out.val_off[base[0]] = uint32_t(base[2]);
       }
       base[0] += 1;
-      base[1] += a.rkey_off[s] - a.rkey_off[s - 1];
-      base[2] += a.rval_off[s] - a.rval_off[s - 1];
+      base[1] += a.raw.key_off[s] - a.raw.key_off[s - 1];
+      base[2] += a.raw.val_off[s] - a.raw.val_off[s - 1];
     }
   }
   if (threadIdx.x == 0) {
     if (ranked) a.opre[nraw] = uint32_t(tot[0]);
-    const TotalCaps caps = a.has_out ? TotalCaps{a.entry_cap, a.key_cap, a.val_cap} : TotalCaps{~0ull, ~0ull, ~0ull};
-    publish_totals(a.stats, tot, caps, a.has_out ? a.okey_off : nullptr, a.has_out ? a.oval_off : nullptr, kSentIfClean, 0,
+    const TotalCaps caps = a.out.on ? TotalCaps{a.out.entry_cap, a.out.key_cap, a.out.val_cap} : TotalCaps{~0ull, ~0ull, ~0ull};
+    publish_totals(a.stats, tot, caps, a.out.on ? a.out.key_off : nullptr, a.out.on ? a.out.val_off : nullptr, kSentIfClean, 0,
                    /*ovf_entries=*/true);
     or_err(a.stats, serr);
     for (uint32_t k = 0; k < 3; ++k) a.stats[4 + k] = a.sstats[k];
@@ -2006,15 +1961,87 @@ __global__ __launch_bounds__(256) void lsm_scan_gather_kernel(LsmScanArgs a) {
     const uint32_t s = a.slot[i];
     if (!s || s > nraw) continue;
     const uint64_t e = s - 1, oi = a.opre[i];
-    if (oi >= a.entry_cap) continue;
-    const uint32_t kl = a.rkey_off[e + 1] - a.rkey_off[e], vl = a.rval_off[e + 1] - a.rval_off[e];
-    const uint32_t ko = a.okey_off[oi], vo = a.oval_off[oi];
+    if (oi >= a.out.entry_cap) continue;
+    const uint32_t kl = a.raw.key_off[e + 1] - a.raw.key_off[e], vl = a.raw.val_off[e + 1] - a.raw.val_off[e];
+    const uint32_t ko = a.out.key_off[oi], vo = a.out.val_off[oi];
     // (the totals passed the capacity check: a place past a capacity is not written)
-    if (uint64_t(ko) + kl > a.key_cap || uint64_t(vo) + vl > a.val_cap) continue;
-    quarter_copy_glb(a.okeys + ko, a.rkeys + a.rkey_off[e], kl, sub);
-    quarter_copy_glb(a.ovals + vo, a.rvals + a.rval_off[e], vl, sub);
-    if (sub == 0) a.ots[oi] = a.rts[e];
+    if (uint64_t(ko) + kl > a.out.key_cap || uint64_t(vo) + vl > a.out.val_cap) continue;
+    quarter_copy_glb(a.out.keys + ko, a.raw.keys + a.raw.key_off[e], kl, sub);
+    quarter_copy_glb(a.out.vals + vo, a.raw.vals + a.raw.val_off[e], vl, sub);
+    if (sub == 0) a.out.ts[oi] = a.raw.ts[e];
   }
+}
+
+// ---------------------------------------------------------------- host: what the entry points share
+// The argument checks (true: LSMBLK_E_INVAL), made before the context is locked.  The opened set:
+// files and index 16-B aligned, and its arrays given when the call reads them.
+bool bad_opened(const OpenedSet& o, bool read) {
+  return (read && o.nsst && (!o.files || !o.file_off || !o.desc)) || (reinterpret_cast<uintptr_t>(o.files) & 15) ||
+         (reinterpret_cast<uintptr_t>(o.index) & 15);
+}
+bool bad_view(const lsmblk_lsm_view* v) {
+  return !v || (v->nl0 && !v->l0) || (v->nlevel && (!v->level_start || !v->level_sst)) ||
+         uint64_t(v->nl0) + v->nlevel >= 0xFFFFFFFFull;
+}
+bool bad_stream(const lsmblk_kv_stream* s) {  // (an absent stream is fine)
+  return s && (!s->key_off || !s->val_off || (s->entry_cap && !s->ts) || (s->key_cap && !s->keys) || (s->val_cap && !s->vals));
+}
+ViewArgs view_args(const lsmblk_lsm_view* v) { return ViewArgs{v->l0, v->nl0, v->nlevel, v->level_sst, v->level_start}; }
+
+// A call's prologue: the context's lock, its device made current, the caller's stream, the stats
+// words zeroed on it.  rc != 0: the call returns it.
+struct CallGuard {
+  std::lock_guard<std::mutex> lock;
+  DeviceGuard dg;
+  hipStream_t st;
+  int rc;
+  CallGuard(lsmblk_ctx* c, void* stream, uint64_t* stats, uint32_t words)
+      : lock(c->mu), dg(c->device, c), st(reinterpret_cast<hipStream_t>(stream)),
+        rc(dg.ok && hipMemsetAsync(stats, 0, words * 8, st) == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP) {}
+};
+
+// The first entry of an offsets array (or of both of a stream's) zeroed: an empty batch's result.
+bool zero_first(uint32_t* off, hipStream_t st) { return !off || hipMemsetAsync(off, 0, 4, st) == hipSuccess; }
+bool zero_first(const lsmblk_kv_stream* s, hipStream_t st) { return !s || (zero_first(s->key_off, st) && zero_first(s->val_off, st)); }
+
+// Grid of a grid-strided kernel that takes `per` items per workgroup: at most 8 workgroups per CU.
+struct GridCap {
+  uint64_t cap;
+  explicit GridCap(const lsmblk_ctx* c) {
+    const int cus = cu_count(c);
+    cap = uint64_t(cus > 0 ? cus : 256) * 8;
+  }
+  uint32_t operator()(uint64_t items, uint64_t per) const {
+    const uint64_t w = (items + per - 1) / per;
+    return uint32_t(w < 1 ? 1 : (w < cap ? w : cap));
+  }
+};
+
+// Workspace regions one after another, each rounded up to 256 bytes: the region's offset.
+struct Carve {
+  uint64_t need = 0;
+  uint64_t operator()(uint64_t bytes) {
+    const uint64_t o = need;
+    need += (bytes + 255) & ~255ull;
+    return o;
+  }
+};
+
+// The scan kernels' workspace: four regions of W and the unit budget.
+void scan_workspace(ScanArgs& a, uint8_t* W, uint64_t o_ubase, uint64_t o_qbad, uint64_t o_hdr, uint64_t o_cnt,
+                    uint64_t budget) {
+  a.ubase = reinterpret_cast<uint32_t*>(W + o_ubase);
+  a.qbad = reinterpret_cast<uint32_t*>(W + o_qbad);
+  a.hdr = reinterpret_cast<uint64_t*>(W + o_hdr);
+  a.ucnt = reinterpret_cast<uint64_t*>(W + o_cnt);
+  a.budget = uint32_t(budget);
+}
+
+// The values of a point-read call's FOUND lookups: their offsets, then the bytes.
+template <class Args>
+void launch_values(const Args& a, const GridCap& grid, hipStream_t st) {
+  LSM_LAUNCH_NAMED("val_scan_kernel", val_scan_kernel<Args>, dim3(1), dim3(1024), 0, st, a);
+  LSM_LAUNCH_NAMED("val_gather_kernel", val_gather_kernel<Args>, dim3(grid(a.nq, 4)), dim3(256), 0, st, a);
 }
 
 }  // namespace
@@ -2024,33 +2051,22 @@ extern "C" {
 int lsmblk_sst_open_batch(lsmblk_ctx* c, const uint8_t* files, const uint64_t* file_off, uint32_t nsst,
                           lsmblk_sst_desc* desc, lsmblk_sst_index* index, uint64_t index_cap, uint64_t* stats,
                           void* stream) {
-  if (!c || !stats || (nsst && (!file_off || !desc || !files)) || (index_cap && !index)) return LSMBLK_E_INVAL;
-  if ((reinterpret_cast<uintptr_t>(files) & 15) || (reinterpret_cast<uintptr_t>(index) & 15) || nsst > 0x3FFFFFFFu)
+  if (!c || !stats || bad_opened(OpenedSet{files, file_off, nsst, desc, index}, true) || (index_cap && !index) ||
+      nsst > 0x3FFFFFFFu)
     return LSMBLK_E_INVAL;
-  std::lock_guard<std::mutex> g(c->mu);
-  DeviceGuard dg(c->device, c);
-  if (!dg.ok) return LSMBLK_E_HIP;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(stats, 0, LSMBLK_STATS_WORDS * 8, st) != hipSuccess) return LSMBLK_E_HIP;
+  CallGuard call(c, stream, stats, LSMBLK_STATS_WORDS);
+  if (call.rc) return call.rc;
+  hipStream_t st = call.st;
   if (nsst == 0) return LSMBLK_OK;
   int rc;
   if ((rc = lsmblk_impl::ensure_crc_tabs(c, st))) return rc;
   // workspace: the CRC range table, the CRCs, the CRC pass's own stats
-  const uint64_t tab_bytes = (8ull * (4ull * nsst + 1) + 255) & ~255ull, crc_bytes = (16ull * nsst + 255) & ~255ull;
-  const uint64_t need = tab_bytes + crc_bytes + 256;
-  if (need > c->sws_cap && (rc = grow(st, &c->sws, &c->sws_cap, need, 1))) return rc;
-  OpenArgs a;
-  a.files = files;
-  a.file_off = file_off;
-  a.nsst = nsst;
-  a.desc = desc;
-  a.index = index;
-  a.index_cap = index_cap;
-  a.tab = reinterpret_cast<uint64_t*>(c->sws);
-  uint32_t* crc = reinterpret_cast<uint32_t*>(c->sws + tab_bytes);
-  uint64_t* cstats = reinterpret_cast<uint64_t*>(c->sws + tab_bytes + crc_bytes);
-  a.crc = crc;
-  a.stats = stats;
+  Carve ws;
+  const uint64_t o_tab = ws(8ull * (4ull * nsst + 1)), o_crc = ws(16ull * nsst), o_cstats = ws(256);
+  if (ws.need > c->sws_cap && (rc = grow(st, &c->sws, &c->sws_cap, ws.need, 1))) return rc;
+  uint32_t* crc = reinterpret_cast<uint32_t*>(c->sws + o_crc);
+  uint64_t* cstats = reinterpret_cast<uint64_t*>(c->sws + o_cstats);
+  const OpenArgs a{files, file_off, nsst, desc, index, index_cap, reinterpret_cast<uint64_t*>(c->sws + o_tab), crc, stats};
   if (hipMemsetAsync(cstats, 0, 32, st) != hipSuccess) return LSMBLK_E_HIP;
   LSM_LAUNCH(sst_open_prep_kernel, dim3(1), dim3(1024), 0, st, a);
   // (the ranges between the sections are flagged in cstats, which nothing reads)
@@ -2065,28 +2081,17 @@ int lsmblk_sst_get_batch(lsmblk_ctx* c, const uint8_t* files, const uint64_t* fi
                          uint32_t flags, lsmblk_get_result* res, uint8_t* vals, uint64_t val_cap, uint32_t* val_off,
                          uint64_t* stats, void* stream) {
   if (!c || !stats || (flags & ~(LSMBLK_GET_NO_FILTER | LSMBLK_GET_MVCC)) || (vals && !val_off)) return LSMBLK_E_INVAL;
-  if (nq && (!q_sst || !qkey_off || !q_ts || !res || (nsst && (!files || !file_off || !desc)))) return LSMBLK_E_INVAL;
-  if ((reinterpret_cast<uintptr_t>(files) & 15) || (reinterpret_cast<uintptr_t>(index) & 15) || nq >= 0xFFFFFFFFull)
-    return LSMBLK_E_INVAL;
-  std::lock_guard<std::mutex> g(c->mu);
-  DeviceGuard dg(c->device, c);
-  if (!dg.ok) return LSMBLK_E_HIP;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(stats, 0, LSMBLK_STATS_WORDS * 8, st) != hipSuccess) return LSMBLK_E_HIP;
-  if (nq == 0) {
-    if (vals && hipMemsetAsync(val_off, 0, 4, st) != hipSuccess) return LSMBLK_E_HIP;
-    return LSMBLK_OK;
-  }
-  GetArgs a{files, file_off, nsst, desc, index, q_sst, qkeys, qkey_off, q_ts, nq, flags, res, vals, val_cap, val_off, stats};
-  int cus = 256;
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
-  const uint64_t cap = uint64_t(cus > 0 ? cus : 256) * 8, want = (nq + kGetWaves - 1) / kGetWaves;
-  LSM_LAUNCH(sst_get_kernel, dim3(uint32_t(want < cap ? want : cap)), dim3(64 * kGetWaves), 0, st, a);
-  if (vals) {
-    LSM_LAUNCH_NAMED("val_scan_kernel", val_scan_kernel<GetArgs>, dim3(1), dim3(1024), 0, st, a);
-    const uint64_t gw = (nq + 3) / 4;
-    LSM_LAUNCH_NAMED("val_gather_kernel", val_gather_kernel<GetArgs>, dim3(uint32_t(gw < cap ? gw : cap)), dim3(256), 0, st, a);
-  }
+  const OpenedSet o{files, file_off, nsst, desc, index};
+  if (nq && (!q_sst || !qkey_off || !q_ts || !res)) return LSMBLK_E_INVAL;
+  if (bad_opened(o, nq != 0) || nq >= 0xFFFFFFFFull) return LSMBLK_E_INVAL;
+  CallGuard call(c, stream, stats, LSMBLK_STATS_WORDS);
+  if (call.rc) return call.rc;
+  hipStream_t st = call.st;
+  if (nq == 0) return !vals || zero_first(val_off, st) ? LSMBLK_OK : LSMBLK_E_HIP;
+  const GetArgs a{o, {qkeys, qkey_off, q_ts, nq, flags, vals, val_cap, val_off, stats}, q_sst, res};
+  const GridCap grid(c);
+  LSM_LAUNCH(sst_get_kernel, dim3(grid(nq, kGetWaves)), dim3(64 * kGetWaves), 0, st, a);
+  if (vals) launch_values(a, grid, st);
   return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
 }
 
@@ -2095,37 +2100,26 @@ int lsmblk_lsm_get_batch(lsmblk_ctx* c, const uint8_t* files, const uint64_t* fi
                          const uint8_t* qkeys, const uint32_t* qkey_off, const uint64_t* q_ts, uint64_t nq,
                          uint32_t flags, lsmblk_lsm_get_result* res, uint8_t* vals, uint64_t val_cap, uint32_t* val_off,
                          uint64_t* stats, void* stream) {
-  if (!c || !stats || !view || (flags & ~(LSMBLK_GET_MVCC | LSMBLK_LSM_GET_NEWEST)) || (vals && !val_off)) return LSMBLK_E_INVAL;
-  if ((view->nl0 && !view->l0) || (view->nlevel && (!view->level_start || !view->level_sst)) ||
-      uint64_t(view->nl0) + view->nlevel >= 0xFFFFFFFFull)
+  if (!c || !stats || bad_view(view) || (flags & ~(LSMBLK_GET_MVCC | LSMBLK_LSM_GET_NEWEST)) || (vals && !val_off))
     return LSMBLK_E_INVAL;
-  if (nq && (!qkey_off || !q_ts || !res || (nsst && (!files || !file_off || !desc)))) return LSMBLK_E_INVAL;
-  if ((reinterpret_cast<uintptr_t>(files) & 15) || (reinterpret_cast<uintptr_t>(index) & 15) || nq >= 0xFFFFFFFFull)
-    return LSMBLK_E_INVAL;
-  std::lock_guard<std::mutex> g(c->mu);
-  DeviceGuard dg(c->device, c);
-  if (!dg.ok) return LSMBLK_E_HIP;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(stats, 0, LSMBLK_STATS_WORDS * 8, st) != hipSuccess) return LSMBLK_E_HIP;
-  if (nq == 0) {
-    if (vals && hipMemsetAsync(val_off, 0, 4, st) != hipSuccess) return LSMBLK_E_HIP;
-    return LSMBLK_OK;
-  }
+  const OpenedSet o{files, file_off, nsst, desc, index};
+  if (nq && (!qkey_off || !q_ts || !res)) return LSMBLK_E_INVAL;
+  if (bad_opened(o, nq != 0) || nq >= 0xFFFFFFFFull) return LSMBLK_E_INVAL;
+  CallGuard call(c, stream, stats, LSMBLK_STATS_WORDS);
+  if (call.rc) return call.rc;
+  hipStream_t st = call.st;
+  if (nq == 0) return !vals || zero_first(val_off, st) ? LSMBLK_OK : LSMBLK_E_HIP;
   int rc;
   if (256 > c->sws_cap && (rc = grow(st, &c->sws, &c->sws_cap, 256, 1))) return rc;
   if (hipMemsetAsync(c->sws, 0, 256, st) != hipSuccess) return LSMBLK_E_HIP;
-  LsmGetArgs a{files, file_off, nsst, desc, index, view->l0, view->nl0, view->nlevel, view->level_sst, view->level_start,
-               qkeys, qkey_off, q_ts, nq, flags, res, vals, val_cap, val_off, stats, reinterpret_cast<uint32_t*>(c->sws)};
-  int cus = 256;
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
-  const uint64_t cap = uint64_t(cus > 0 ? cus : 256) * 8, want = (nq + kGetWaves - 1) / kGetWaves;
-  LSM_LAUNCH(lsm_view_check_kernel, dim3(32), dim3(256), 0, st, a);
-  LSM_LAUNCH(lsm_get_kernel, dim3(uint32_t(want < cap ? want : cap)), dim3(64 * kGetWaves), 0, st, a);
-  if (vals) {
-    LSM_LAUNCH_NAMED("val_scan_kernel", val_scan_kernel<LsmGetArgs>, dim3(1), dim3(1024), 0, st, a);
-    const uint64_t gw = (nq + 3) / 4;
-    LSM_LAUNCH_NAMED("val_gather_kernel", val_gather_kernel<LsmGetArgs>, dim3(uint32_t(gw < cap ? gw : cap)), dim3(256), 0, st, a);
-  }
+  const ViewArgs v = view_args(view);
+  uint32_t* const vflag = reinterpret_cast<uint32_t*>(c->sws);
+  const LsmGetArgs a{o, v, {qkeys, qkey_off, q_ts, nq, flags, vals, val_cap, val_off, stats}, res, vflag};
+  const ViewCheckArgs vc{o, v, stats, vflag};
+  const GridCap grid(c);
+  LSM_LAUNCH(lsm_view_check_kernel, dim3(32), dim3(256), 0, st, vc);
+  LSM_LAUNCH(lsm_get_kernel, dim3(grid(nq, kGetWaves)), dim3(64 * kGetWaves), 0, st, a);
+  if (vals) launch_values(a, grid, st);
   return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
 }
 
@@ -2135,68 +2129,24 @@ int lsmblk_sst_scan_batch(lsmblk_ctx* c, const uint8_t* files, const uint64_t* f
                           const uint32_t* q_bound, uint64_t nq, uint32_t flags, lsmblk_scan_result* res,
                           const lsmblk_kv_stream* out, uint32_t* seg_start, uint64_t* stats, void* stream) {
   if (!c || !stats || !seg_start || (flags & ~(LSMBLK_SCAN_NO_FILTER | LSMBLK_SCAN_MVCC))) return LSMBLK_E_INVAL;
-  if (nq && (!q_sst || !q_bound || !lkey_off || !ukey_off || !res || (nsst && (!files || !file_off || !desc))))
-    return LSMBLK_E_INVAL;
-  if (out && (!out->key_off || !out->val_off || (out->entry_cap && !out->ts) || (out->key_cap && !out->keys) ||
-              (out->val_cap && !out->vals)))
-    return LSMBLK_E_INVAL;
-  if ((reinterpret_cast<uintptr_t>(files) & 15) || (reinterpret_cast<uintptr_t>(index) & 15) || nq > 0x7FFFFFFFull)
-    return LSMBLK_E_INVAL;
-  std::lock_guard<std::mutex> g(c->mu);
-  DeviceGuard dg(c->device, c);
-  if (!dg.ok) return LSMBLK_E_HIP;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(stats, 0, LSMBLK_STATS_WORDS * 8, st) != hipSuccess) return LSMBLK_E_HIP;
-  if (nq == 0) {
-    if (hipMemsetAsync(seg_start, 0, 4, st) != hipSuccess) return LSMBLK_E_HIP;
-    if (out && (hipMemsetAsync(out->key_off, 0, 4, st) != hipSuccess || hipMemsetAsync(out->val_off, 0, 4, st) != hipSuccess))
-      return LSMBLK_E_HIP;
-    return LSMBLK_OK;
-  }
+  const OpenedSet o{files, file_off, nsst, desc, index};
+  if (nq && (!q_sst || !q_bound || !lkey_off || !ukey_off || !res)) return LSMBLK_E_INVAL;
+  if (bad_stream(out) || bad_opened(o, nq != 0) || nq > 0x7FFFFFFFull) return LSMBLK_E_INVAL;
+  CallGuard call(c, stream, stats, LSMBLK_STATS_WORDS);
+  if (call.rc) return call.rc;
+  hipStream_t st = call.st;
+  if (nq == 0) return zero_first(seg_start, st) && zero_first(out, st) ? LSMBLK_OK : LSMBLK_E_HIP;
   // workspace: ubase | qbad | hdr | ucnt, sized by nq and the unit budget alone
   const uint64_t budget = c->scan_units, units = nq + budget;
-  const uint64_t o_qbad = (4 * (nq + 1) + 255) & ~255ull, o_hdr = o_qbad + ((4 * nq + 255) & ~255ull);
-  const uint64_t o_cnt = o_hdr + 256, need = o_cnt + 24 * units;
+  Carve ws;
+  const uint64_t o_ubase = ws(4 * (nq + 1)), o_qbad = ws(4 * nq), o_hdr = ws(256);
+  const uint64_t o_cnt = ws.need, need = o_cnt + 24 * units;  // (the last region: not rounded up)
   int rc;
   if (need > c->sws_cap && (rc = grow(st, &c->sws, &c->sws_cap, need, 1))) return rc;
-  ScanArgs a;
-  a.files = files;
-  a.file_off = file_off;
-  a.nsst = nsst;
-  a.desc = desc;
-  a.index = index;
-  a.q_sst = q_sst;
-  a.lkeys = lkeys;
-  a.lkey_off = lkey_off;
-  a.ukeys = ukeys;
-  a.ukey_off = ukey_off;
-  a.q_bound = q_bound;
-  a.nq = nq;
-  a.flags = flags;
-  a.res = res;
-  a.okeys = out ? out->keys : nullptr;
-  a.okey_off = out ? out->key_off : nullptr;
-  a.ovals = out ? out->vals : nullptr;
-  a.oval_off = out ? out->val_off : nullptr;
-  a.ots = out ? out->ts : nullptr;
-  a.entry_cap = out ? out->entry_cap : 0;
-  a.key_cap = out ? out->key_cap : 0;
-  a.val_cap = out ? out->val_cap : 0;
-  a.has_out = out ? 1u : 0u;
-  a.seg_start = seg_start;
-  a.ubase = reinterpret_cast<uint32_t*>(c->sws);
-  a.qbad = reinterpret_cast<uint32_t*>(c->sws + o_qbad);
-  a.hdr = reinterpret_cast<uint64_t*>(c->sws + o_hdr);
-  a.ucnt = reinterpret_cast<uint64_t*>(c->sws + o_cnt);
-  a.budget = uint32_t(budget);
-  a.stats = stats;
-  a.nq_dev = nullptr;
-  a.parent = nullptr;
-  int cus = 256;
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
-  const uint64_t cap = uint64_t(cus > 0 ? cus : 256) * 8;
-  const uint64_t qw = (nq + kGetWaves - 1) / kGetWaves, uw = (units + kGetWaves - 1) / kGetWaves;
-  launch_scan<false>(a, uint32_t(qw < cap ? qw : cap), uint32_t(uw < cap ? uw : cap), out != nullptr, st);
+  ScanArgs a{o, {lkeys, lkey_off, ukeys, ukey_off, q_bound}, q_sst, nq, flags, res, dev_stream(out), seg_start, stats};
+  scan_workspace(a, c->sws, o_ubase, o_qbad, o_hdr, o_cnt, budget);
+  const GridCap grid(c);
+  launch_scan<false>(a, grid(nq, kGetWaves), grid(units, kGetWaves), out != nullptr, st);
   return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
 }
 
@@ -2206,49 +2156,30 @@ int lsmblk_lsm_scan_batch(lsmblk_ctx* c, const uint8_t* files, const uint64_t* f
                           const uint32_t* q_bound, const uint64_t* q_ts, uint64_t nq, uint32_t flags, uint64_t sub_cap,
                           lsmblk_lsm_scan_result* res, const lsmblk_kv_stream* raw, const lsmblk_kv_stream* out,
                           uint32_t* seg_start, uint64_t* stats, void* stream) {
-  if (!c || !stats || !seg_start || !view || (flags & ~(LSMBLK_SCAN_MVCC | LSMBLK_LSM_SCAN_NEWEST)) || (out && !raw))
+  if (!c || !stats || !seg_start || bad_view(view) || (flags & ~(LSMBLK_SCAN_MVCC | LSMBLK_LSM_SCAN_NEWEST)) || (out && !raw))
     return LSMBLK_E_INVAL;
   const bool newest = (flags & LSMBLK_LSM_SCAN_NEWEST) != 0;  // (implies the corrected landing)
-  if ((view->nl0 && !view->l0) || (view->nlevel && (!view->level_start || !view->level_sst)) ||
-      uint64_t(view->nl0) + view->nlevel >= 0xFFFFFFFFull)
+  const OpenedSet o{files, file_off, nsst, desc, index};
+  if (nq && (!q_bound || !lkey_off || !ukey_off || !res)) return LSMBLK_E_INVAL;
+  if (bad_stream(raw) || bad_stream(out) || bad_opened(o, nq != 0) || nq > 0x7FFFFFFFull || sub_cap > 0x7FFFFFFFull)
     return LSMBLK_E_INVAL;
-  if (nq && (!q_bound || !lkey_off || !ukey_off || !res || (nsst && (!files || !file_off || !desc)))) return LSMBLK_E_INVAL;
-  for (const lsmblk_kv_stream* s : {raw, out})
-    if (s && (!s->key_off || !s->val_off || (s->entry_cap && !s->ts) || (s->key_cap && !s->keys) || (s->val_cap && !s->vals)))
-      return LSMBLK_E_INVAL;
-  if ((reinterpret_cast<uintptr_t>(files) & 15) || (reinterpret_cast<uintptr_t>(index) & 15) || nq > 0x7FFFFFFFull ||
-      sub_cap > 0x7FFFFFFFull)
-    return LSMBLK_E_INVAL;
-  std::lock_guard<std::mutex> g(c->mu);
-  DeviceGuard dg(c->device, c);
-  if (!dg.ok) return LSMBLK_E_HIP;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(stats, 0, LSMBLK_LSM_SCAN_STATS_WORDS * 8, st) != hipSuccess) return LSMBLK_E_HIP;
-  if (nq == 0) {
-    if (hipMemsetAsync(seg_start, 0, 4, st) != hipSuccess) return LSMBLK_E_HIP;
-    for (const lsmblk_kv_stream* s : {raw, out})
-      if (s && (hipMemsetAsync(s->key_off, 0, 4, st) != hipSuccess || hipMemsetAsync(s->val_off, 0, 4, st) != hipSuccess))
-        return LSMBLK_E_HIP;
-    return LSMBLK_OK;
-  }
+  CallGuard call(c, stream, stats, LSMBLK_LSM_SCAN_STATS_WORDS);
+  if (call.rc) return call.rc;
+  hipStream_t st = call.st;
+  if (nq == 0) return zero_first(seg_start, st) && zero_first(raw, st) && zero_first(out, st) ? LSMBLK_OK : LSMBLK_E_HIP;
   // workspace, sized by nq, sub_cap, the unit budget and raw's entry capacity alone:
   //   head (vflag, nsub, the table scans' stats) | pbad | mcnt | scnt | sbase | sub_q | sub_sst | sseg | table scan
   //   results | the scan kernels' ubase | qbad | hdr | ucnt | slot | opre
   const uint64_t budget = c->scan_units, units = sub_cap + budget;
   const uint64_t slot_cap = raw ? (raw->entry_cap < 0xFFFFFFFFull ? raw->entry_cap : 0xFFFFFFFFull) : 0;
-  uint64_t need = 0;
-  auto carve = [&](uint64_t bytes) {
-    const uint64_t o = need;
-    need += (bytes + 255) & ~255ull;
-    return o;
-  };
-  const uint64_t o_head = carve(256), o_pbad = carve(4 * nq), o_mcnt = carve(4 * nq), zero_end = need;
+  Carve carve;
+  const uint64_t o_head = carve(256), o_pbad = carve(4 * nq), o_mcnt = carve(4 * nq), zero_end = carve.need;
   const uint64_t o_scnt = carve(4 * nq), o_sbase = carve(4 * (nq + 1)), o_subq = carve(4 * sub_cap), o_subs = carve(4 * sub_cap);
   const uint64_t o_sseg = carve(4 * (sub_cap + 1)), o_sres = carve(sizeof(lsmblk_scan_result) * sub_cap);
   const uint64_t o_ubase = carve(4 * (sub_cap + 1)), o_qbad = carve(4 * sub_cap), o_hdr = carve(256), o_cnt = carve(24 * units);
   const uint64_t o_slot = carve(4 * slot_cap), o_opre = carve(4 * (slot_cap + 1));
   int rc;
-  if (need > c->sws_cap && (rc = grow(st, &c->sws, &c->sws_cap, need, 1))) return rc;
+  if (carve.need > c->sws_cap && (rc = grow(st, &c->sws, &c->sws_cap, carve.need, 1))) return rc;
   uint8_t* const W = c->sws;
   if (hipMemsetAsync(W, 0, zero_end, st) != hipSuccess) return LSMBLK_E_HIP;
   // (a slot no entry ranks to -- only files that are not in key order leave one -- keeps nothing)
@@ -2256,61 +2187,13 @@ int lsmblk_lsm_scan_batch(lsmblk_ctx* c, const uint8_t* files, const uint64_t* f
   auto u32p = [&](uint64_t o) { return reinterpret_cast<uint32_t*>(W + o); };
   uint64_t* const head = reinterpret_cast<uint64_t*>(W + o_head);
 
-  LsmGetArgs v{};
-  v.files = files;
-  v.file_off = file_off;
-  v.nsst = nsst;
-  v.desc = desc;
-  v.index = index;
-  v.l0 = view->l0;
-  v.nl0 = view->nl0;
-  v.nlevel = view->nlevel;
-  v.level_sst = view->level_sst;
-  v.level_start = view->level_start;
-  v.nq = nq;
-  v.stats = stats;
-  v.vflag = u32p(o_head);
+  // the three argument structs, from the same opened set, view and bounds
+  const ViewArgs v = view_args(view);
+  const BoundArgs b{lkeys, lkey_off, ukeys, ukey_off, q_bound};
+  const ViewCheckArgs vc{o, v, stats, u32p(o_head)};
 
-  LsmScanArgs a{};
-  a.files = files;
-  a.desc = desc;
-  a.nsst = nsst;
-  a.l0 = view->l0;
-  a.nl0 = view->nl0;
-  a.nlevel = view->nlevel;
-  a.level_sst = view->level_sst;
-  a.level_start = view->level_start;
-  a.lkeys = lkeys;
-  a.lkey_off = lkey_off;
-  a.ukeys = ukeys;
-  a.ukey_off = ukey_off;
-  a.q_bound = q_bound;
-  a.q_ts = q_ts;
-  a.nq = nq;
-  a.sub_cap = sub_cap;
-  a.res = res;
-  if (raw) {
-    a.rkeys = raw->keys;
-    a.rkey_off = raw->key_off;
-    a.rvals = raw->vals;
-    a.rval_off = raw->val_off;
-    a.rts = raw->ts;
-    a.has_raw = 1;
-  }
-  if (out) {
-    a.okeys = out->keys;
-    a.okey_off = out->key_off;
-    a.ovals = out->vals;
-    a.oval_off = out->val_off;
-    a.ots = out->ts;
-    a.entry_cap = out->entry_cap;
-    a.key_cap = out->key_cap;
-    a.val_cap = out->val_cap;
-    a.has_out = 1;
-  }
-  a.seg_start = seg_start;
-  a.stats = stats;
-  a.vflag = u32p(o_head);
+  LsmScanArgs a{o, v, b, q_ts, nq, sub_cap, res, dev_stream(raw), dev_stream(out), seg_start, stats};
+  a.vflag = vc.vflag;
   a.nsub = head + 1;
   a.sstats = head + 4;
   a.pbad = u32p(o_pbad);
@@ -2326,62 +2209,27 @@ int lsmblk_lsm_scan_batch(lsmblk_ctx* c, const uint8_t* files, const uint64_t* f
   a.slot_cap = slot_cap;
 
   // the table scans: range_overlap already passed (NO_FILTER), bounds and kinds of the scan's range
-  ScanArgs s{};
-  s.files = files;
-  s.file_off = file_off;
-  s.nsst = nsst;
-  s.desc = desc;
-  s.index = index;
-  s.q_sst = a.sub_sst;
-  s.lkeys = lkeys;
-  s.lkey_off = lkey_off;
-  s.ukeys = ukeys;
-  s.ukey_off = ukey_off;
-  s.q_bound = q_bound;
-  s.nq = 0;
-  s.flags = (newest ? LSMBLK_SCAN_MVCC : flags) | LSMBLK_SCAN_NO_FILTER;
-  s.res = reinterpret_cast<lsmblk_scan_result*>(W + o_sres);
-  if (raw) {
-    s.okeys = raw->keys;
-    s.okey_off = raw->key_off;
-    s.ovals = raw->vals;
-    s.oval_off = raw->val_off;
-    s.ots = raw->ts;
-    s.entry_cap = raw->entry_cap;
-    s.key_cap = raw->key_cap;
-    s.val_cap = raw->val_cap;
-    s.has_out = 1;
-  }
-  s.seg_start = a.sseg;
-  s.ubase = u32p(o_ubase);
-  s.qbad = u32p(o_qbad);
-  s.hdr = reinterpret_cast<uint64_t*>(W + o_hdr);
-  s.ucnt = reinterpret_cast<uint64_t*>(W + o_cnt);
-  s.budget = uint32_t(budget);
-  s.stats = a.sstats;
+  // (their count is on the device: nq_dev; the output stream is raw, its runs' starts sseg)
+  ScanArgs s{o, b, a.sub_sst, 0, (newest ? LSMBLK_SCAN_MVCC : flags) | LSMBLK_SCAN_NO_FILTER,
+             reinterpret_cast<lsmblk_scan_result*>(W + o_sres), a.raw, a.sseg, a.sstats};
+  scan_workspace(s, W, o_ubase, o_qbad, o_hdr, o_cnt, budget);
   s.nq_dev = a.nsub;
   s.parent = a.sub_q;
 
-  int cus = 256;
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
-  const uint64_t cap = uint64_t(cus > 0 ? cus : 256) * 8;
-  auto grid = [&](uint64_t items, uint64_t per) {
-    const uint64_t w = (items + per - 1) / per;
-    return dim3(uint32_t(w < 1 ? 1 : (w < cap ? w : cap)));
-  };
-  LSM_LAUNCH(lsm_view_check_kernel, dim3(32), dim3(256), 0, st, v);
-  LSM_LAUNCH_NAMED("lsm_scan_expand_count_kernel", lsm_scan_expand_kernel<false>, grid(nq, kGetWaves), dim3(64 * kGetWaves), 0,
-                   st, a);
+  const GridCap grid(c);
+  LSM_LAUNCH(lsm_view_check_kernel, dim3(32), dim3(256), 0, st, vc);
+  LSM_LAUNCH_NAMED("lsm_scan_expand_count_kernel", lsm_scan_expand_kernel<false>, dim3(grid(nq, kGetWaves)),
+                   dim3(64 * kGetWaves), 0, st, a);
   LSM_LAUNCH(lsm_scan_subs_kernel, dim3(1), dim3(kScanWg), 0, st, a);
-  LSM_LAUNCH_NAMED("lsm_scan_expand_fill_kernel", lsm_scan_expand_kernel<true>, grid(nq, kGetWaves), dim3(64 * kGetWaves), 0,
-                   st, a);
-  launch_scan<true>(s, grid(sub_cap, kGetWaves).x, grid(units, kGetWaves).x, raw != nullptr, st);
+  LSM_LAUNCH_NAMED("lsm_scan_expand_fill_kernel", lsm_scan_expand_kernel<true>, dim3(grid(nq, kGetWaves)),
+                   dim3(64 * kGetWaves), 0, st, a);
+  launch_scan<true>(s, grid(sub_cap, kGetWaves), grid(units, kGetWaves), raw != nullptr, st);
   if (raw && newest)
-    LSM_LAUNCH_NAMED("lsm_scan_rank_newest_kernel", lsm_scan_rank_kernel<true>, grid(slot_cap, 256), dim3(256), 0, st, a);
+    LSM_LAUNCH_NAMED("lsm_scan_rank_newest_kernel", lsm_scan_rank_kernel<true>, dim3(grid(slot_cap, 256)), dim3(256), 0, st, a);
   else if (raw)
-    LSM_LAUNCH_NAMED("lsm_scan_rank_kernel", lsm_scan_rank_kernel<false>, grid(slot_cap, 256), dim3(256), 0, st, a);
+    LSM_LAUNCH_NAMED("lsm_scan_rank_kernel", lsm_scan_rank_kernel<false>, dim3(grid(slot_cap, 256)), dim3(256), 0, st, a);
   LSM_LAUNCH(lsm_scan_offsets_kernel, dim3(1), dim3(kScanWg), 0, st, a);
-  if (out) LSM_LAUNCH(lsm_scan_gather_kernel, grid(slot_cap, 16), dim3(256), 0, st, a);
+  if (out) LSM_LAUNCH(lsm_scan_gather_kernel, dim3(grid(slot_cap, 16)), dim3(256), 0, st, a);
   return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
 }
 

@@ -125,43 +125,6 @@ __device__ __forceinline__ void lds_read16(const uint8_t* base, uint32_t x, uint
 // cache policy of the staging loads (default; nt loads measured no gain)
 constexpr int kLdAux = 0;
 
-struct BlockHdr {
-  uint32_t len, n, data_end, fks;
-  bool ok;
-};
-
-template <class Img>
-__device__ __forceinline__ BlockHdr parse_hdr(const Img& im, uint32_t len) {
-  BlockHdr h{len, 0, 0, 0, true};
-  if (len < 2) { h.ok = false; return h; }
-  h.n = im.u16(len - 2);
-  if (2 + 2 * h.n > len) { h.ok = false; h.n = 0; return h; }
-  h.data_end = len - 2 - 2 * h.n;
-  if (h.n) {
-    // get_first_key (iterator.rs:23-34) parses the entry at data position 0.
-    if (h.data_end < 4) { h.ok = false; return h; }
-    h.fks = im.u16(2);
-    if (4 + h.fks + 8 > h.data_end) h.ok = false;
-  }
-  return h;
-}
-
-// Corrected seek_to_offset (iterator.rs:125-139) with the validation rules of DESIGN.md.
-template <class Img>
-__device__ __forceinline__ bool parse_entry(const Img& im, const BlockHdr& h, uint32_t k,
-                                            uint32_t& off, uint32_t& p, uint32_t& s, uint32_t& vl) {
-  off = im.u16(h.data_end + 2 * k);
-  bool ok = off + 4 <= h.data_end;
-  const uint32_t w = im.le32(off);  // BE16 p | BE16 s
-  p = bswap16(w & 0xFFFF);
-  s = bswap16(w >> 16);
-  ok = ok && (off + 4 + s + 10 <= h.data_end) && (p <= h.fks) && (p + s > 0);
-  vl = im.u16(off + 12 + s);
-  ok = ok && (off + 14 + s + vl <= h.data_end);
-  if (!ok) { p = s = vl = 0; }
-  return ok;
-}
-
 // Simple path: per-entry lanes, any block size / entry count, byte-granular stores.
 template <class Img>
 __device__ void dec_simple_outputs(const DecodeArgs& a, const Img& im, const BlockHdr& h,
@@ -4564,8 +4527,7 @@ int encode_locked(lsmblk_ctx* c, const lsmblk_kv_stream* in, const uint64_t* dn,
     if (blk_cap >= 1 && hipMemsetAsync(blk_off, 0, 8, st) != hipSuccess) return LSMBLK_E_HIP;
     return LSMBLK_OK;
   }
-  int cus = 256;
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
+  const int cus = cu_count(c);
   // the fused walk + emit (A/B only: the walk's instructions compete with emit's for the same
   // issue slots): per-segment slots, blocks no larger than emit's LDS image
   const bool fused = slots && !framed && block_size <= 4096 && c->fuse_on;
@@ -4940,8 +4902,8 @@ int launch_crc(lsmblk_ctx* c, const uint8_t* blocks, const uint64_t* blk_off, ui
   a.crc = crc;
   a.tabs = static_cast<const CrcTabs*>(c->crc_tabs);
   a.stats = stats;
-  int cus = 256, per_cu = 0;
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
+  const int cus = cu_count(c);
+  int per_cu = 0;
 #ifndef LSMBLK_XCRC_OLD
   if (!agg && !sections) {  // the plain pass: one 16-wave workgroup per CU (the replicated tables fill the LDS)
     CrcStreamArgs b;
@@ -4988,8 +4950,7 @@ int launch_crc_frames(lsmblk_ctx* c, uint8_t* out, const uint64_t* blk_off, cons
   b.frame_out = out;
   b.sz = blk_sz;
   b.dnblk = stats;
-  int cus = 256;
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
+  const int cus = cu_count(c);
   const uint64_t want = (nblk_max + 4 * kCsWaves - 1) / (4 * kCsWaves);
   const uint32_t grid = uint32_t(want < uint64_t(cus) ? (want ? want : 1) : uint64_t(cus));
   LSM_LAUNCH(crc_stream_kernel, dim3(grid), dim3(64 * kCsWaves), 0, st, b);

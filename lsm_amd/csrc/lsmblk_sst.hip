@@ -278,8 +278,11 @@ __global__ __launch_bounds__(256) void sst_bloom_kernel(SstArgs a) {
 // binary search (mid = low + (high - low) / 2, returning at the first probe whose key compares
 // equal -- with several versions of a user key in the block that is not necessarily the first of
 // them), keys reconstructed as first_key[..prefix] || suffix (seek_to_offset :125-132) and compared
-// ts-agnostically (src/key.rs:77-81).  A block or probed entry that breaks the decode rules
-//  reports LSMBLK_ERR_MALFORMED and the block's entry count.
+// ts-agnostically (src/key.rs:77-81).  A block or probed entry that breaks the rules of parse_hdr /
+// parse_entry (lsmblk_dev.hpp, the one definition) reports LSMBLK_ERR_MALFORMED and the block's
+// entry count.  The rules are restated here, every load behind its check: a lane per query reads
+// through a plain pointer, where the shared parse_entry's load-then-check would reach up to 64 KiB
+// past a malformed block.  tests/test_gpu_block_rules.py holds this copy to every rule.
 struct SeekArgs {
   const uint8_t* blocks;
   const uint64_t* blk_off;
