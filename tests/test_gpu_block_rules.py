@@ -75,6 +75,17 @@ def test_verifying_decode(name):
     check_decode(name, tail=4, verify=True)
 
 
+@pytest.mark.parametrize("name", brc.NAMES)
+def test_two_pass_verifying_decode(name):
+    """crc_kernel<true>'s count_block, the fused count of the two-pass verifying decode."""
+    ctx = batch._ctx(0)
+    assert lib().lsmblk_debug_set(ctx, 3, 1) == 0  # LSMBLK_DEBUG_TWO_PASS_DECODE
+    try:
+        check_decode(name, tail=4, verify=True)
+    finally:
+        lib().lsmblk_debug_set(ctx, 3, 0)
+
+
 @pytest.mark.parametrize("name", SST_NAMES)
 def test_seek(name):
     c = brc.case(name)

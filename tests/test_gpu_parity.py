@@ -412,7 +412,9 @@ def test_crc32_blocks_match_crc32fast():
     """Per-block CRC-32 of SST framing (src/table/builder.rs:120-122, src/table.rs:226-230)
     against the oracle's CRC-32 (pinned to crc32fast by the reference's MANIFEST records) and
     zlib: empty and 1-3-byte blocks, 64-B and 4-KiB boundaries, multi-chunk blocks, ragged
-    random lengths, unaligned block starts, and enough blocks for the persistent stride."""
+    random lengths, unaligned block starts.  (5321 blocks are 84 workgroups of crc_stream_kernel,
+    four blocks per wave: no wave takes a second group.  The persistent stride is entered by
+    test_gpu_crc_paths.test_streaming_persistent_loop.)"""
     rng = np.random.default_rng(31)
     lens = [0, 1, 2, 3, 4, 5, 63, 64, 65, 127, 128, 4095, 4096, 4097, 8191, 8192, 8193, 65536, 70001, 0, 17]
     lens += [int(x) for x in rng.integers(0, 9000, 300)] + [int(x) for x in rng.integers(0, 200, 5000)]
@@ -653,12 +655,24 @@ def _framed(ref_blocks, ref_off, corrupt=None):
     return np.frombuffer(b"".join(parts), np.uint8).copy(), np.array(off, np.uint64)
 
 
+@pytest.mark.parametrize("mode", ["lagged", "two_pass"])
 @pytest.mark.parametrize("gen,n,bs", [("mixed", 6000, 65536), ("uniform", 20000, 256), ("mixed", 3000, 4096)])
-def test_verifying_decode_counts_in_the_crc_pass(gen, n, bs):
-    """verify=True replaces dec_count_kernel by the CRC pass's fused count (blocks over one 4-KiB
-    CRC chunk count from global memory): same KV stream, block entry index, and MALFORMED for a
+def test_verifying_decode_counts_in_the_crc_pass(gen, n, bs, mode):
+    """verify=True in both decode modes.  lagged (the default): crc_stream_kernel and the checksum
+    test, then the lagged decode with its own count.  two_pass (LSMBLK_DEBUG_TWO_PASS_DECODE):
+    crc_kernel<true>, whose fused count replaces dec_count_kernel (blocks over one 4-KiB CRC chunk
+    count from global memory).  Either way: same KV stream, block entry index, and MALFORMED for a
     block that breaks the decode rules under a correct checksum."""
-    from lsm_amd._lib import LSMBLK_E_MALFORMED
+    from lsm_amd._lib import LSMBLK_E_MALFORMED, lib
+    ctx = batch._ctx(0)
+    assert lib().lsmblk_debug_set(ctx, 3, int(mode == "two_pass")) == 0
+    try:
+        _verifying_decode_counts(gen, n, bs)
+    finally:
+        lib().lsmblk_debug_set(ctx, 3, 0)
+
+
+def _verifying_decode_counts(gen, n, bs):
     g = {"mixed": synth.gen_mixed, "uniform": synth.gen_uniform}[gen]
     kv = O.KV(*g(n, seed=23))
     seg = synth.segments_by_bytes(kv.key_off, kv.val_off, 1 << 20)
@@ -952,7 +966,7 @@ def test_framed_encode_is_the_sst_builders_data_section():
 
 def test_framed_encode_u_large_equals_blocks_and_crcs():
     """At 400 K entries: the framed encode == the packed encode with lsmblk_crc32_batch's CRCs
-    interleaved (and a sample of them == zlib), the verifying framed decode reads it back."""
+    interleaved (and every one of them == zlib), the verifying framed decode reads it back."""
     kv = O.KV(*synth.gen_uniform(400_000, seed=33))
     seg = synth.segments_by_bytes(kv.key_off, kv.val_off, 2 << 20)
     d = to_dev(kv)
@@ -968,7 +982,7 @@ def test_framed_encode_u_large_equals_blocks_and_crcs():
     ends = fo[1:] - 4
     got_crc = (f[ends[:, None] + np.arange(4)].astype(np.uint32) << np.array([24, 16, 8, 0], np.uint32)).sum(1)
     np.testing.assert_array_equal(got_crc.astype(np.uint32), crc)
-    for i in range(0, nblk, max(1, nblk // 50)):
+    for i in range(nblk):
         assert zlib.crc32(b[o[i]:o[i + 1]].tobytes()) == int(crc[i])
     dkv = batch.decode_blocks(out, off, tail=4, verify=True)
     assert dkv.n == kv.n
