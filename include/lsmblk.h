@@ -338,9 +338,31 @@ int lsmblk_compact_filter_batch(lsmblk_ctx* ctx, const lsmblk_kv_stream* in, uin
  *                           are dropped), and for a key in both, skip_b drops b's 1st, 3rd, ... version
  *                           and the 2nd, 4th, ... come BEFORE a's versions.  Byte-identical to what the
  *                           reference binary's compaction writes for the same inputs.
- * DESIGN.md §3 tabulates the input classes on which the two differ. */
+ *   LSMBLK_MERGE_NEWEST     the snapshot-preserving merge, the write-side counterpart of
+ *                           LSMBLK_LSM_GET_NEWEST / LSMBLK_LSM_SCAN_NEWEST: the stable merge of all runs by
+ *                           (key ascending bytewise, a shorter key less; ts descending as u64; run index
+ *                           ascending; position in the run ascending).  EVERY input entry is in the
+ *                           output (stats[0] == in->n; lsmblk_compact_batch: stats[4] == in->n); two
+ *                           entries with the same (key, ts) in two runs are both emitted, the lower run
+ *                           first -- nothing is deduplicated.  Precondition: every run is in (key
+ *                           ascending, ts descending) order, as a builder fed by a memtable flush or a
+ *                           compaction writes it; it is checked on run-adjacent pairs (entry g against
+ *                           g-1 of the same run), and a key that decreases or an equal key with a larger
+ *                           ts reports LSMBLK_ERR_MALFORMED (the output is then unspecified).  The rules,
+ *                           the SST rotation and the block packing are those of the other modes; over
+ *                           this order "a key's versions newest first" holds across runs, so every
+ *                           version above the watermark is kept from whichever run; of a key's versions
+ *                           at or below it only the first in merged order (on an equal ts: the lower
+ *                           run's); and with bottom_level a tombstone goes, with everything older, only
+ *                           when it is at or below the watermark and the key's newest version over ALL
+ *                           runs.  A snapshot read (newest = 1) at any read_ts >= watermark returns the
+ *                           same rows before and after such a compaction without prefix filters; after a
+ *                           LSMBLK_MERGE_RUNS one it need not (a key's versions in the other runs are
+ *                           gone).  No reference counterpart: Key's Ord ignores the ts there.
+ * DESIGN.md §3 tabulates the input classes on which the modes differ. */
 #define LSMBLK_MERGE_RUNS 0u
 #define LSMBLK_MERGE_TWO_LEVEL 1u
+#define LSMBLK_MERGE_NEWEST 2u
 
 /* k-way merge of sorted runs (SURVEY.md §8 f, row 2) with MergeIterator's semantics
  * (src/iterators/merge_iterator.rs:59-184) = LSMBLK_MERGE_RUNS: run r = entries [run_start[r], run_start[r+1]) of `in`
@@ -356,7 +378,8 @@ int lsmblk_compact_filter_batch(lsmblk_ctx* ctx, const lsmblk_kv_stream* in, uin
  * tiles hold u16 key lengths, as the block format does).  Asynchronous. */
 int lsmblk_merge_batch(lsmblk_ctx* ctx, const lsmblk_kv_stream* in, const uint32_t* run_start, uint32_t nrun,
                        const lsmblk_kv_stream* out, uint64_t* stats, void* stream);
-/* lsmblk_merge_batch in merge_mode LSMBLK_MERGE_RUNS or LSMBLK_MERGE_TWO_LEVEL (run nrun-1 = b). */
+/* lsmblk_merge_batch in merge_mode LSMBLK_MERGE_RUNS, LSMBLK_MERGE_TWO_LEVEL (run nrun-1 = b) or
+ * LSMBLK_MERGE_NEWEST (every entry, by key / ts descending / run); any other value: LSMBLK_E_INVAL. */
 int lsmblk_merge_batch_ex(lsmblk_ctx* ctx, const lsmblk_kv_stream* in, const uint32_t* run_start, uint32_t nrun,
                           uint32_t merge_mode, const lsmblk_kv_stream* out, uint64_t* stats, void* stream);
 
@@ -381,14 +404,16 @@ typedef struct {
   const uint8_t* prefixes;
   const uint32_t* prefix_off;  /* u32[nprefix+1] */
   uint32_t block_size;
-  uint32_t merge_mode;         /* LSMBLK_MERGE_RUNS (0) or LSMBLK_MERGE_TWO_LEVEL (run nrun-1 = the lower level) */
+  uint32_t merge_mode;         /* LSMBLK_MERGE_RUNS (0), LSMBLK_MERGE_TWO_LEVEL (run nrun-1 = the lower level) or
+                                  LSMBLK_MERGE_NEWEST (the snapshot-preserving merge) */
   uint64_t target_sst_size;
 } lsmblk_compact_opts;
 
 #define LSMBLK_COMPACT_STATS_WORDS 8
 /* compact_generate_sst (src/compact.rs:223-311) on the device for sorted runs already decoded
  * into `in` (run_start as for lsmblk_merge_batch): merge (opts->merge_mode: the run-priority merge,
- * or the reference's TwoMergeIterator with the lower level as the last run) -> keep/drop rules ->
+ * the reference's TwoMergeIterator with the lower level as the last run, or the snapshot-preserving
+ * LSMBLK_MERGE_NEWEST) -> keep/drop rules ->
  * SST rotation -> SsTableBuilder block packing.  `kept` receives the entries handed to
  * SsTableBuilder::add (capacities as for decode); the blocks of every SST are written packed to
  * `out` (16-byte aligned) with blk_off (u64[blk_cap], nblk+1 values), as lsmblk_encode_batch writes
@@ -431,14 +456,14 @@ typedef struct {
 uint64_t lsmblk_shard_halo_entries(uint32_t block_size);
 
 /* lsmblk_compact_batch's merge + rules + gather, restricted to keys in *range (NULL: all keys;
- * opts->merge_mode must be LSMBLK_MERGE_RUNS here; both modes: lsmblk_compact_merge_batch_ex):
+ * opts->merge_mode must be LSMBLK_MERGE_RUNS here; every mode: lsmblk_compact_merge_batch_ex):
  * kept receives this range's entries handed to SsTableBuilder::add.  stats: [0] kept entries [1] key
  * bytes [2] value bytes [3] error flags [4] merged entries.  Asynchronous. */
 int lsmblk_compact_merge_batch(lsmblk_ctx* ctx, const lsmblk_kv_stream* in, const uint32_t* run_start, uint32_t nrun,
                                const lsmblk_compact_opts* opts, const lsmblk_key_range* range,
                                const lsmblk_kv_stream* kept, uint64_t* stats, void* stream);
 
-/* The same in either merge mode.  LSMBLK_MERGE_TWO_LEVEL (TwoMergeIterator as written, run nrun-1 = b):
+/* The same in every merge mode.  LSMBLK_MERGE_TWO_LEVEL (TwoMergeIterator as written, run nrun-1 = b):
  * the stream ends at b's last key kb over the WHOLE compaction (two_merge_iterator.rs:32-42,60-66), so
  * each range says where kb lies (the caller all-gathers every range's local b-run end):
  *   LSMBLK_TWO_END_IN_RANGE  kb is in this range (or range is NULL): b's local last key is kb;
@@ -446,8 +471,8 @@ int lsmblk_compact_merge_batch(lsmblk_ctx* ctx, const lsmblk_kv_stream* in, cons
  *   LSMBLK_TWO_END_BELOW     kb lies below the range, or b is empty everywhere: no a-entry survives;
  * and kept_same (device u8[kept->entry_cap]) receives every kept entry's same_as_last_key of the
  * compact_generate_sst loop (src/compact.rs:279; with the two-level order it is not "same key as the
- * previous kept entry"), which the rotation needs: lsmblk_shard_rotation_prepare_ex.  LSMBLK_MERGE_RUNS:
- * two_end is ignored and kept_same may be NULL. */
+ * previous kept entry"), which the rotation needs: lsmblk_shard_rotation_prepare_ex.  LSMBLK_MERGE_RUNS and
+ * LSMBLK_MERGE_NEWEST: two_end is ignored and kept_same may be NULL. */
 #define LSMBLK_TWO_END_IN_RANGE 0u
 #define LSMBLK_TWO_END_ABOVE 1u
 #define LSMBLK_TWO_END_BELOW 2u
@@ -466,7 +491,8 @@ int lsmblk_shard_rotation_prepare(lsmblk_ctx* ctx, const lsmblk_kv_stream* ext, 
                                   uint32_t block_size, uint64_t target_sst_size, uint32_t sst_cap, void* stream);
 /* The same with ext_same (device u8[ext->n], two-level merges): every ext entry's same_as_last_key,
  * the range's own from lsmblk_compact_merge_batch_ex's kept_same, the halo's from the ranks that
- * own it.  NULL: "same key as the previous entry" (LSMBLK_MERGE_RUNS). */
+ * own it.  NULL: "same key as the previous entry" (LSMBLK_MERGE_RUNS, LSMBLK_MERGE_NEWEST: it holds over
+ * a (key, ts descending) stream too). */
 int lsmblk_shard_rotation_prepare_ex(lsmblk_ctx* ctx, const lsmblk_kv_stream* ext, const uint8_t* ext_same,
                                      uint64_t n_own, uint32_t flags, uint32_t block_size, uint64_t target_sst_size,
                                      uint32_t sst_cap, void* stream);

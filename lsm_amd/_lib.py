@@ -30,6 +30,7 @@ LSMBLK_DEBUG_ENCODE_FUSED = 8
 LSMBLK_SHARD_LAST = 1
 LSMBLK_MERGE_RUNS = 0
 LSMBLK_MERGE_TWO_LEVEL = 1
+LSMBLK_MERGE_NEWEST = 2
 LSMBLK_TWO_END_IN_RANGE = 0
 LSMBLK_TWO_END_ABOVE = 1
 LSMBLK_TWO_END_BELOW = 2

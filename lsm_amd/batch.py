@@ -591,8 +591,9 @@ def read_filter(kv: KVStream, seg_start, read_ts, stream=None):
 def merge_into(kv: KVStream, run_start: torch.Tensor, nrun: int, out: KVStream, stats, stream=None,
                merge_mode=LSMBLK_MERGE_RUNS):
     """Asynchronous merge of the runs of kv into preallocated `out` (no host sync): MergeIterator
-    (LSMBLK_MERGE_RUNS) or the reference's TwoMergeIterator with run nrun-1 as b
-    (LSMBLK_MERGE_TWO_LEVEL)."""
+    (LSMBLK_MERGE_RUNS), the reference's TwoMergeIterator with run nrun-1 as b
+    (LSMBLK_MERGE_TWO_LEVEL), or every entry of every run by (key ascending, ts descending, run,
+    position) (LSMBLK_MERGE_NEWEST; every run in (key, ts descending) order, else MALFORMED)."""
     dev = _dev_index(run_start)
     kv.check(dev, "kv")
     _need(run_start, torch.int32, "run_start", dev, nrun + 1)
@@ -607,7 +608,10 @@ def merge_runs(kv: KVStream, run_start, stream=None, merge_mode=LSMBLK_MERGE_RUN
     """MergeIterator (reference src/iterators/merge_iterator.rs:59-184) over the sorted runs
     kv[run_start[r]:run_start[r+1]] (run 0 = highest priority) -> the merged KVStream.
     merge_mode=LSMBLK_MERGE_TWO_LEVEL: TwoMergeIterator(MergeIterator(runs[:-1]), runs[-1])
-    (two_merge_iterator.rs:19-93 as written)."""
+    (two_merge_iterator.rs:19-93 as written).  merge_mode=LSMBLK_MERGE_NEWEST: the snapshot-preserving
+    merge, every entry of every run by (key ascending, ts descending as u64, run, position); nothing
+    is dropped or deduplicated, and a run that is not in (key, ts descending) order raises
+    LSMBLK_E_MALFORMED."""
     dev = torch.device("cuda", _dev_index(kv.key_off))
     rs = _u32_table(run_start, dev)
     kb, vb = kv.byte_sizes()
@@ -688,7 +692,10 @@ def _opts_c(opts):
 
 def compact_opts(watermark=0, bottom_level=False, prefixes=(), block_size=4096, target_sst_size=2 << 20,
                  device="cuda", merge_mode=LSMBLK_MERGE_RUNS):
-    """Options of lsmblk_compact_batch (prefix tables staged on the device once)."""
+    """Options of lsmblk_compact_batch (prefix tables staged on the device once).  merge_mode:
+    LSMBLK_MERGE_RUNS, LSMBLK_MERGE_TWO_LEVEL (run nrun-1 = the lower level) or LSMBLK_MERGE_NEWEST
+    (the rules then keep, from whichever run, every version above the watermark and the newest at
+    or below it, so snapshot reads at read_ts >= watermark are unchanged by the compaction)."""
     return dict(watermark=watermark, bottom_level=bottom_level, block_size=block_size,
                 target_sst_size=target_sst_size, _pfx=_prefix_tables(prefixes, torch.device(device)),
                 _npfx=len(prefixes), merge_mode=merge_mode)
@@ -697,7 +704,9 @@ def compact_opts(watermark=0, bottom_level=False, prefixes=(), block_size=4096, 
 def compact_runs(kv: KVStream, run_start, watermark=0, bottom_level=False, prefixes=(), block_size=4096,
                  target_sst_size=2 << 20, stream=None, merge_mode=LSMBLK_MERGE_RUNS):
     """compact_generate_sst (reference src/compact.rs:223-311) on the device over the sorted runs
-    of kv (run 0 = highest priority): merge (merge_mode, see include/lsmblk.h), keep/drop rules,
+    of kv (run 0 = highest priority): merge (merge_mode, see include/lsmblk.h: the run-priority
+    merge, the reference's two-level one, or LSMBLK_MERGE_NEWEST, under which stats[4] == kv.n and a
+    snapshot reader at or above the watermark sees the same rows afterwards), keep/drop rules,
     SST rotation, block packing.  Returns dict(kept KVStream, blocks, blk_off, sst_start, sst_blk,
     stats)."""
     dev = torch.device("cuda", _dev_index(kv.key_off))
@@ -733,7 +742,8 @@ def compact_merge_into(kv: KVStream, run_start: torch.Tensor, nrun: int, opts: d
     """Asynchronous lsmblk_compact_merge_batch_ex: merge + rules restricted to key_range (a KeyRangeC
     or None) into preallocated `kept`.  stats: int64[5] device.  Two-level merges (opts merge_mode):
     two_end (LSMBLK_TWO_END_*) and kept_same (uint8 device tensor, the loop's same_as_last_key per
-    kept entry) as include/lsmblk.h describes."""
+    kept entry) as include/lsmblk.h describes.  LSMBLK_MERGE_NEWEST, like LSMBLK_MERGE_RUNS, ignores
+    two_end and needs no kept_same: "same key as the previous entry" holds over its order."""
     dev = _dev_index(run_start)
     kv.check(dev, "kv")
     _need(run_start, torch.int32, "run_start", dev, nrun + 1)

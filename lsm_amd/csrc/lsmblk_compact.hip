@@ -15,7 +15,18 @@
 // and its merged position is the number of surviving entries with a smaller key plus its rank
 // inside its own run's group.
 //
+// LSMBLK_MERGE_NEWEST is the merge a snapshot reader needs instead: the stable merge of all runs by
+// (key ascending, ts descending as u64, run index, position), every input entry in the output -- the
+// order of lsm_scan_rank_kernel<true> (lsmblk_get.hip) over whole runs.  Every run must itself be in
+// (key ascending, ts descending) order; run_order_kernel checks that on run-adjacent pairs before
+// anything relies on it.  Candidates, bounds, the tile scan and perm_kernel are shared (equal keys
+// never straddle tiles, so all versions of a key from all runs meet in one tile); the tile kernels
+// have a NEWEST instantiation without survival: an entry's rank is its index in its run's sub-range
+// plus, per other run, the entries ordered before it (one binary search, the ts read from global
+// memory on key ties only).
+//
 // Kernels ("sample merge path"):
+//   run_order_kernel   LSMBLK_MERGE_NEWEST only: every entry against its run predecessor
 //   cand_rank_kernel   every kMS-th entry of every run is a candidate; its rank among all the
 //                      candidates by (key, run, index) comes from binary searches in the other
 //                      runs' candidate lists; candidates are scattered into sorted order
@@ -130,6 +141,8 @@ struct MergeArgs {
   uint64_t* mstats;         // [0] merged entries [1] candidates (tiles) [3] error flags [5] big tiles
   uint32_t two;             // LSMBLK_MERGE_TWO_LEVEL: TwoMergeIterator(runs 0..nrun-2, run nrun-1)
   uint32_t two_end;         // two-level, key-range shard: LSMBLK_TWO_END_* (where b's last key lies)
+  const uint64_t* ts;       // n: the input entries' ts (LSMBLK_MERGE_NEWEST: the tie-break on equal keys)
+  uint32_t newest;          // LSMBLK_MERGE_NEWEST: every entry survives, ordered by (key, ts desc, run)
 };
 
 // LSMBLK_MERGE_TWO_LEVEL: the reference's compact() input, TwoMergeIterator(a = MergeIterator(upper
@@ -246,6 +259,22 @@ __global__ __launch_bounds__(256) void cand_key_kernel(MergeArgs a) {
   if (p >= a.n) return;  // (a bad run table: cand_rank_kernel merges nothing)
   a.ck[c] = a.k16[p];
   a.cklen[c] = a.key_off[p + 1] - a.key_off[p];
+}
+
+// LSMBLK_MERGE_NEWEST's precondition, entry g against entry g - 1 of the same run: the key must not
+// decrease, and on an equal key the ts must not increase (a builder's output).  Checked on the runs
+// themselves, so the report does not depend on where a mis-ranked entry lands in the merged order.
+__global__ __launch_bounds__(256) void run_order_kernel(MergeArgs a) {
+  __shared__ uint32_t s_rs[kMaxRuns + 1], s_cb[kMaxRuns + 1];
+  load_runs(a, s_rs, s_cb);
+  const uint64_t g64 = uint64_t(blockIdx.x) * 256 + threadIdx.x;
+  if (g64 == 0 || g64 >= a.n) return;
+  const uint32_t g = uint32_t(g64), r = find_run(s_rs, a.nrun, g);
+  if (g == s_rs[r]) return;  // the first entry of its run (a bad run table: cand_rank_kernel reports it)
+  const GKeys K = gkeys(a.keys, a.key_off[a.n]);
+  const uint32_t p0 = a.key_off[g - 1], p1 = a.key_off[g], p2 = a.key_off[g + 1];
+  const int c = kcmp16(a, K, a.k16[g - 1], p1 - p0, g - 1, a.k16[g], p2 - p1, g);
+  if (c > 0 || (c == 0 && a.ts[g - 1] < a.ts[g])) or_err(a.mstats, LSMBLK_ERR_MALFORMED);
 }
 
 __global__ __launch_bounds__(256) void cand_rank_kernel(MergeArgs a) {
@@ -422,13 +451,46 @@ __device__ __forceinline__ void tile_survivor_prefix(const MergeArgs& a, MTileLd
 }
 
 // LDS fast path: 128 threads per tile; every key's first 16 bytes in LDS.
-template <uint32_t E, uint32_t T>
+// NEWEST: no survival and no survivor prefix; the rank counts, per other run, the entries ordered
+// before (x, ts_x, r) -- key < x, or key == x and (ts > ts_x, or ts == ts_x and r2 < r).  A run is in
+// (key, ts desc) order, so that is one binary search; the ts (global memory: the LDS tables stay as
+// they are) is read only where the keys tie, and the tie-break itself is compares, not branches.
+template <uint32_t E, uint32_t T, bool NEWEST>
 __device__ void merge_tile_lds(const MergeArgs& a, MTileLdsT<E>& L, uint32_t t) {
   TileHdr& H = L.h;
   const uint32_t tid = threadIdx.x, nrun = a.nrun, total = H.total;
   const GKeys G = gkeys(a.keys, a.key_off[a.n]);
   load_tile_keys<E, T>(a, L, G);
   __syncthreads();
+  if constexpr (NEWEST) {
+    for (uint32_t u = tid; u < total; u += T) {
+      const uint32_t r = find_run(H.tb, nrun, u), g = H.lo[r] + u - H.tb[r];
+      const u32x4 x = L.kw[u];
+      const uint32_t xl = L.klen[u];
+      const uint64_t tsx = a.ts[g];
+      uint32_t rank = u - H.tb[r];
+      for (uint32_t r2 = 0; r2 < nrun; ++r2) {
+        const uint32_t b = H.tb[r2], g2 = H.lo[r2];
+        if (r2 == r || H.tb[r2 + 1] == b) continue;
+        uint32_t lo = 0, hi = H.tb[r2 + 1] - b;
+        while (lo < hi) {
+          const uint32_t mid = (lo + hi) >> 1;
+          const int c = kcmp16s(a, G, L.kw[b + mid], L.klen[b + mid], g2 + mid, x, xl, g);
+          bool before = c < 0;
+          if (c == 0) {
+            const uint64_t tm = a.ts[g2 + mid];
+            before = (tm > tsx) | ((tm == tsx) & (r2 < r));
+          }
+          if (before) lo = mid + 1;
+          else hi = mid;
+        }
+        rank += lo;
+      }
+      a.mrank[g] = rank;
+    }
+    if (tid == 0) a.tcnt[t] = total;
+    return;
+  }
   // first index of run r2's sub-range whose key is >= (x, xl) (> with upper)
   auto bound = [&](uint32_t r2, const u32x4& x, uint32_t xl, uint32_t xg, bool upper) -> uint32_t {
     const uint32_t b = H.tb[r2];
@@ -488,6 +550,8 @@ __device__ void merge_tile_lds(const MergeArgs& a, MTileLdsT<E>& L, uint32_t t) 
 // Global path (a tile of more than kMTE entries: many versions of one key, or many runs), one
 // wave: keys compared in global memory, survival kept in mrank[] and the survivor prefix in
 // sp[], handed between lanes through L2 (sc1 stores / loads, drained with vmcnt(0)).
+// NEWEST: the rank alone, by the same order as merge_tile_lds<.., true> (no hand-over between lanes).
+template <bool NEWEST>
 __device__ void merge_tile_global(const MergeArgs& a, TileHdr& H, uint32_t* rsv, uint32_t t) {  // rsv: LDS, kMaxRuns
   const uint32_t l = lane_id(), nrun = a.nrun, total = H.total;
   const GKeys G = gkeys(a.keys, a.key_off[a.n]);
@@ -496,6 +560,36 @@ __device__ void merge_tile_global(const MergeArgs& a, TileHdr& H, uint32_t* rsv,
     len = a.key_off[g + 1] - p;
     return p;
   };
+  if constexpr (NEWEST) {
+    for (uint32_t u = l; u < total; u += 64) {
+      const uint32_t r = find_run(H.tb, nrun, u), k = u - H.tb[r], g = H.lo[r] + k;
+      uint32_t xl;
+      const uint32_t xp = kpos(r, k, xl);
+      const uint64_t tsx = a.ts[g];
+      uint32_t rank = k;
+      for (uint32_t r2 = 0; r2 < nrun; ++r2) {
+        if (r2 == r) continue;
+        uint32_t lo = 0, hi = H.tb[r2 + 1] - H.tb[r2];
+        while (lo < hi) {
+          const uint32_t mid = (lo + hi) >> 1;
+          uint32_t ml;
+          const uint32_t mp = kpos(r2, mid, ml);
+          const int c = key_cmp(G, mp, ml, xp, xl);
+          bool before = c < 0;
+          if (c == 0) {
+            const uint64_t tm = a.ts[H.lo[r2] + mid];
+            before = (tm > tsx) | ((tm == tsx) & (r2 < r));
+          }
+          if (before) lo = mid + 1;
+          else hi = mid;
+        }
+        rank += lo;
+      }
+      a.mrank[g] = rank;
+    }
+    if (l == 0) a.tcnt[t] = total;
+    return;
+  }
   auto bound = [&](uint32_t r, uint32_t xp, uint32_t xl, bool upper) -> uint32_t {
     uint32_t lo = 0, hi = H.tb[r + 1] - H.tb[r];
     while (lo < hi) {
@@ -582,6 +676,7 @@ __device__ void merge_tile_global(const MergeArgs& a, TileHdr& H, uint32_t* rsv,
   if (l == 0) a.tcnt[t] = carry;
 }
 
+template <bool NEWEST>
 __global__ __launch_bounds__(kMTT) void merge_tile_kernel(MergeArgs a) {
   __shared__ MTileLds L;
   // (tiles past the candidate count are empty: bounds_kernel.  The XCD-aware tile order of
@@ -595,7 +690,7 @@ __global__ __launch_bounds__(kMTT) void merge_tile_kernel(MergeArgs a) {
     return;
   }
   if (total <= kMTE) {
-    merge_tile_lds<kMTE, kMTT>(a, L, t);
+    merge_tile_lds<kMTE, kMTT, NEWEST>(a, L, t);
   } else if (threadIdx.x == 0) {  // to merge_big_kernel
     const uint64_t i = atomicAdd(reinterpret_cast<unsigned long long*>(a.mstats + 5), 1ull);
     a.big[i] = t;
@@ -604,6 +699,7 @@ __global__ __launch_bounds__(kMTT) void merge_tile_kernel(MergeArgs a) {
 
 // The tiles merge_tile_kernel left (over kMTE entries): kBigGrid persistent workgroups over the
 // list, LDS tables up to kBigTE entries, the one-wave global path beyond.
+template <bool NEWEST>
 __global__ __launch_bounds__(kBigTT) void merge_big_kernel(MergeArgs a) {
   __shared__ MTileBigLds L;
   __shared__ uint32_t rsv[kMaxRuns];  // the global path's per-run survivor counts
@@ -612,8 +708,8 @@ __global__ __launch_bounds__(kBigTT) void merge_big_kernel(MergeArgs a) {
     const uint32_t t = a.big[i];
     if (threadIdx.x < 64) tile_ranges(a, L.h, t);
     __syncthreads();
-    if (L.h.total <= kBigTE) merge_tile_lds<kBigTE, kBigTT>(a, L, t);
-    else if (threadIdx.x < 64) merge_tile_global(a, L.h, rsv, t);
+    if (L.h.total <= kBigTE) merge_tile_lds<kBigTE, kBigTT, NEWEST>(a, L, t);
+    else if (threadIdx.x < 64) merge_tile_global<NEWEST>(a, L.h, rsv, t);
     __syncthreads();
   }
 }
@@ -1961,9 +2057,10 @@ int ensure_ws(lsmblk_ctx* c, uint64_t bytes, hipStream_t st) {
 int merge_gather_locked(lsmblk_ctx* c, const lsmblk_kv_stream* in, const uint32_t* run_start, uint32_t nrun,
                         uint32_t rules, uint64_t wm, int bottom, const uint8_t* pfx, const uint32_t* pfx_off,
                         uint32_t npfx, const lsmblk_key_range* range, const lsmblk_kv_stream* out, uint64_t* stats,
-                        hipStream_t st, MergePlan* plan_out, uint32_t two, uint32_t two_end = LSMBLK_TWO_END_IN_RANGE,
+                        hipStream_t st, MergePlan* plan_out, uint32_t mode, uint32_t two_end = LSMBLK_TWO_END_IN_RANGE,
                         uint8_t* ksame_out = nullptr, GatherArgs* defer = nullptr) {
   const uint64_t n = in->n;
+  const uint32_t two = mode == LSMBLK_MERGE_TWO_LEVEL, newest = mode == LSMBLK_MERGE_NEWEST;
   MergePlan P = plan_merge(nullptr, n, nrun);
   int rc = ensure_ws(c, P.bytes, st);
   if (rc) return rc;
@@ -1977,6 +2074,8 @@ int merge_gather_locked(lsmblk_ctx* c, const lsmblk_kv_stream* in, const uint32_
   m.nrun = nrun;
   m.two = two;
   m.two_end = two_end;
+  m.ts = in->ts;
+  m.newest = newest;
   if (hipMemsetAsync(stats, 0, LSMBLK_STATS_WORDS * 8, st) != hipSuccess) return LSMBLK_E_HIP;
   if (n == 0) {
     LSM_LAUNCH(merge_empty_kernel, dim3(1), dim3(64), 0, st, m.mstats, out->key_off, out->val_off,
@@ -1987,12 +2086,18 @@ int merge_gather_locked(lsmblk_ctx* c, const lsmblk_kv_stream* in, const uint32_
   const uint32_t nc = m.nc_max;
   LSM_LAUNCH(key16_kernel, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, st, m.keys, m.key_off, n,
              const_cast<u32x4*>(m.k16), m.mstats + 3);
+  if (newest) LSM_LAUNCH(run_order_kernel, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, st, m);
   LSM_LAUNCH(cand_key_kernel, dim3((nc + 255) / 256), dim3(256), 0, st, m);
   LSM_LAUNCH(cand_rank_kernel, dim3((nc + 255) / 256), dim3(256), 0, st, m);
   const uint64_t nb = (uint64_t(nc) + 1) * nrun;
   LSM_LAUNCH(bounds_kernel, dim3(uint32_t((nb + 255) / 256)), dim3(256), 0, st, m);
-  LSM_LAUNCH(merge_tile_kernel, dim3(nc), dim3(kMTT), 0, st, m);
-  LSM_LAUNCH(merge_big_kernel, dim3(std::min(nc, kBigGrid)), dim3(kBigTT), 0, st, m);
+  if (newest) {
+    LSM_LAUNCH_NAMED("merge_tile_kernel<newest>", merge_tile_kernel<true>, dim3(nc), dim3(kMTT), 0, st, m);
+    LSM_LAUNCH_NAMED("merge_big_kernel<newest>", merge_big_kernel<true>, dim3(std::min(nc, kBigGrid)), dim3(kBigTT), 0, st, m);
+  } else {
+    LSM_LAUNCH_NAMED("merge_tile_kernel", merge_tile_kernel<false>, dim3(nc), dim3(kMTT), 0, st, m);
+    LSM_LAUNCH_NAMED("merge_big_kernel", merge_big_kernel<false>, dim3(std::min(nc, kBigGrid)), dim3(kBigTT), 0, st, m);
+  }
   LSM_LAUNCH(tscan_part_kernel, dim3((nc + kTScan - 1) / kTScan), dim3(256), 0, st, m);
   LSM_LAUNCH(tscan_top_kernel, dim3(1), dim3(1024), 0, st, m);
   LSM_LAUNCH(perm_kernel, dim3(nc), dim3(64), 0, st, m);
@@ -2261,7 +2366,7 @@ int lsmblk_compact_merge_batch_ex(lsmblk_ctx* c, const lsmblk_kv_stream* in, con
   int rc = check_merge_args(c, in, run_start, nrun, kept, stats);
   if (rc) return rc;
   if (!o || (o->nprefix && (!o->prefixes || !o->prefix_off))) return LSMBLK_E_INVAL;
-  if (o->merge_mode != LSMBLK_MERGE_RUNS && o->merge_mode != LSMBLK_MERGE_TWO_LEVEL) return LSMBLK_E_INVAL;
+  if (o->merge_mode > LSMBLK_MERGE_NEWEST) return LSMBLK_E_INVAL;
   const uint32_t two = o->merge_mode == LSMBLK_MERGE_TWO_LEVEL;
   if (two_end > LSMBLK_TWO_END_BELOW || (two && !kept_same)) return LSMBLK_E_INVAL;
   if (range && ((range->has_lo && range->lo_len && !range->lo) || (range->has_hi && range->hi_len && !range->hi)))
@@ -2273,7 +2378,8 @@ int lsmblk_compact_merge_batch_ex(lsmblk_ctx* c, const lsmblk_kv_stream* in, con
   if (hipMemsetAsync(stats + 4, 0, 8, st) != hipSuccess) return LSMBLK_E_HIP;
   MergePlan MP{};
   if ((rc = merge_gather_locked(c, in, run_start, nrun, 1, o->watermark, o->bottom_level, o->prefixes, o->prefix_off,
-                                o->nprefix, range, kept, stats, st, &MP, two, two_end, two ? kept_same : nullptr)))
+                                o->nprefix, range, kept, stats, st, &MP, o->merge_mode, two_end,
+                                two ? kept_same : nullptr)))
     return rc;
   if (in->n) LSM_LAUNCH(copy_u64_kernel, dim3(1), dim3(64), 0, st, stats + 4, MP.m.mstats);
   return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
@@ -2362,19 +2468,19 @@ int lsmblk_merge_batch(lsmblk_ctx* c, const lsmblk_kv_stream* in, const uint32_t
   DeviceGuard dg(c->device, c);
   if (!dg.ok) return LSMBLK_E_HIP;
   return merge_gather_locked(c, in, run_start, nrun, 0, 0, 0, nullptr, nullptr, 0, nullptr, out, stats,
-                             reinterpret_cast<hipStream_t>(stream), nullptr, 0);
+                             reinterpret_cast<hipStream_t>(stream), nullptr, LSMBLK_MERGE_RUNS);
 }
 
 int lsmblk_merge_batch_ex(lsmblk_ctx* c, const lsmblk_kv_stream* in, const uint32_t* run_start, uint32_t nrun,
                           uint32_t merge_mode, const lsmblk_kv_stream* out, uint64_t* stats, void* stream) {
   int rc = check_merge_args(c, in, run_start, nrun, out, stats);
   if (rc) return rc;
-  if (merge_mode != LSMBLK_MERGE_RUNS && merge_mode != LSMBLK_MERGE_TWO_LEVEL) return LSMBLK_E_INVAL;
+  if (merge_mode > LSMBLK_MERGE_NEWEST) return LSMBLK_E_INVAL;
   std::lock_guard<std::mutex> g(c->mu);
   DeviceGuard dg(c->device, c);
   if (!dg.ok) return LSMBLK_E_HIP;
   return merge_gather_locked(c, in, run_start, nrun, 0, 0, 0, nullptr, nullptr, 0, nullptr, out, stats,
-                             reinterpret_cast<hipStream_t>(stream), nullptr, merge_mode == LSMBLK_MERGE_TWO_LEVEL);
+                             reinterpret_cast<hipStream_t>(stream), nullptr, merge_mode);
 }
 
 int lsmblk_sst_rotation_batch(lsmblk_ctx* c, const lsmblk_kv_stream* in, uint32_t block_size,
@@ -2414,7 +2520,7 @@ int lsmblk_compact_batch(lsmblk_ctx* c, const lsmblk_kv_stream* in, const uint32
   if (!o || !out || !blk_off || !sst_start || !sst_blk || sst_cap < 2 || blk_cap == 0) return LSMBLK_E_INVAL;
   if (o->block_size == 0 || o->target_sst_size == 0 || (o->nprefix && (!o->prefixes || !o->prefix_off)))
     return LSMBLK_E_INVAL;
-  if (o->merge_mode != LSMBLK_MERGE_RUNS && o->merge_mode != LSMBLK_MERGE_TWO_LEVEL) return LSMBLK_E_INVAL;
+  if (o->merge_mode > LSMBLK_MERGE_NEWEST) return LSMBLK_E_INVAL;
   if ((reinterpret_cast<uintptr_t>(out) & 15) != 0) return LSMBLK_E_INVAL;
   const uint32_t two = o->merge_mode == LSMBLK_MERGE_TWO_LEVEL;
   std::lock_guard<std::mutex> g(c->mu);
@@ -2440,7 +2546,8 @@ int lsmblk_compact_batch(lsmblk_ctx* c, const lsmblk_kv_stream* in, const uint32
   MergePlan MP{};
   GatherArgs G{};
   if ((rc = merge_gather_locked(c, in, run_start, nrun, 1, o->watermark, o->bottom_level, o->prefixes, o->prefix_off,
-                                o->nprefix, nullptr, kept, fst, st, &MP, two, LSMBLK_TWO_END_IN_RANGE, nullptr, &G)))
+                                o->nprefix, nullptr, kept, fst, st, &MP, o->merge_mode, LSMBLK_TWO_END_IN_RANGE, nullptr,
+                                &G)))
     return rc;
   R = plan_rot(c->cws, M.bytes, n, o->target_sst_size, o->block_size);
   LSM_LAUNCH(gate_kernel, dim3(1), dim3(64), 0, st, fst, (const uint64_t*)(MP.m.mstats + 3), R.dn);

@@ -213,6 +213,7 @@ class RangeShard:
         self.kv, self.opts = kv, opts
         self.stream = stream if stream is not None else torch.cuda.current_stream(self.dev)
         self.ctx = batch.OwnCtx(self.dev.index)
+        # (LSMBLK_MERGE_NEWEST is driven like LSMBLK_MERGE_RUNS: no b end, no same_as_last_key stream)
         self.two = opts.get("merge_mode", LSMBLK_MERGE_RUNS) == LSMBLK_MERGE_TWO_LEVEL
         self.lo, self.hi = (bytes(lo) if lo is not None else None), (bytes(hi) if hi is not None else None)
         self.two_end = LSMBLK_TWO_END_IN_RANGE  # two-level: set from the whole compaction's b end (set_b_end)

@@ -668,6 +668,14 @@ class SstSet:
         return {f: r[f].copy() for f in LSM_SCAN_FIELDS}, rows
 
 
+def open_compacted(r, device="cuda", stream=None):
+    """The SSTs of a batch.compact_runs result as files, opened: (SstSet, its one-level LsmView) --
+    what a reader sees once the compaction's output has replaced its inputs."""
+    files, off = sst_files(r["blocks"], r["blk_off"], r["sst_blk"], r["sst_start"], r["kept"], stream)
+    ss = SstSet(files, off, device, stream)
+    return ss, ss.view([], [list(range(ss.nsst))])
+
+
 def view_sub_cap(view, nq):
     """Table scans a batch of nq ranges over the view can expand into at most: every table, every range."""
     return nq * (len(view.l0) + sum(len(lv) for lv in view.levels))
