@@ -51,13 +51,14 @@ def _ctx_for(device: int, stream_ptr: int) -> _Ctx:
         return c
 
 
-def release_contexts(device: int = None):
-    """Destroy the cached per-(device, stream) contexts (all, or those of `device`) after their
-    work is done.  Each context keeps its own decode / encode / compaction / SST workspaces, which
-    reach several GiB for 4 GiB batches, so a caller cycling through many streams releases them
-    here; the next call on a stream creates a fresh context."""
+def release_contexts(device: int = None, stream=None):
+    """Destroy the cached per-(device, stream) contexts (all, those of `device`, or the one of
+    `stream`) after their work is done.  Each context keeps its own decode / encode / compaction /
+    SST workspaces, which reach several GiB for 4 GiB batches, so a caller cycling through many
+    streams releases them here; the next call on a stream creates a fresh context."""
     with _ctx_lock:
-        keys = [k for k in _ctxs if device is None or k[0] == device]
+        keys = [k for k in _ctxs if (device is None or k[0] == device) and
+                (stream is None or k[1] == stream.cuda_stream)]
         for k in keys:
             c = _ctxs.pop(k)
             with c.lock:  # waits for a call in progress on it (batch wrappers hold the lock)

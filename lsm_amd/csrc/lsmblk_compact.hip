@@ -1993,19 +1993,6 @@ __global__ __launch_bounds__(256) void rot_finish_kernel(RotArgs a) {
 }
 
 // ---------------------------------------------------------------- host side
-// Carve the context's compaction arena (grown on demand, which synchronizes).
-struct Carve {
-  uint8_t* base;
-  uint64_t off = 0;
-  Carve(uint8_t* b, uint64_t o = 0) : base(b), off(o) {}
-  template <typename T>
-  T* take(uint64_t count) {
-    T* p = reinterpret_cast<T*>(base + off);
-    off = (off + count * sizeof(T) + 255) & ~uint64_t(255);
-    return p;
-  }
-};
-
 struct MergePlan {
   MergeArgs m;
   uint32_t* keep;
@@ -2048,39 +2035,47 @@ MergePlan plan_merge(uint8_t* base, uint64_t n, uint32_t nrun) {
   return P;
 }
 
-int ensure_ws(lsmblk_ctx* c, uint64_t bytes, hipStream_t st) {
-  if (bytes <= c->cws_cap) return LSMBLK_OK;
-  return grow(st, &c->cws, &c->cws_cap, bytes, 1);
-}
-
 // merge + (rules | keep all) + gather into `out`; stats as lsmblk_compact_filter_batch's.
-int merge_gather_locked(lsmblk_ctx* c, const lsmblk_kv_stream* in, const uint32_t* run_start, uint32_t nrun,
-                        uint32_t rules, uint64_t wm, int bottom, const uint8_t* pfx, const uint32_t* pfx_off,
-                        uint32_t npfx, const lsmblk_key_range* range, const lsmblk_kv_stream* out, uint64_t* stats,
-                        hipStream_t st, MergePlan* plan_out, uint32_t mode, uint32_t two_end = LSMBLK_TWO_END_IN_RANGE,
-                        uint8_t* ksame_out = nullptr, GatherArgs* defer = nullptr) {
+struct MergeReq {
+  hipStream_t st = nullptr;
+  const lsmblk_kv_stream* in = nullptr;
+  const uint32_t* run_start = nullptr;
+  uint32_t nrun = 0;
+  uint32_t mode = LSMBLK_MERGE_RUNS;
+  const lsmblk_compact_opts* rules = nullptr;  // the compaction rules (watermark, bottom level, prefixes); null: keep all
+  const lsmblk_key_range* range = nullptr;
+  uint32_t two_end = LSMBLK_TWO_END_IN_RANGE;
+  const lsmblk_kv_stream* out = nullptr;
+  uint64_t* stats = nullptr;
+  uint8_t* ksame_out = nullptr;   // two-level with rules: same_as_last_key per kept entry (null: the plan's)
+  MergePlan* plan_out = nullptr;  // the workspace the call carved
+  GatherArgs* defer = nullptr;    // the kept bytes are left to the caller (mwrite_bytes)
+};
+int merge_gather_locked(lsmblk_ctx* c, const MergeReq& q) {
+  const lsmblk_kv_stream *const in = q.in, *const out = q.out;
+  hipStream_t st = q.st;
   const uint64_t n = in->n;
-  const uint32_t two = mode == LSMBLK_MERGE_TWO_LEVEL, newest = mode == LSMBLK_MERGE_NEWEST;
-  MergePlan P = plan_merge(nullptr, n, nrun);
-  int rc = ensure_ws(c, P.bytes, st);
+  const uint32_t nrun = q.nrun, rules = q.rules != nullptr;
+  const uint32_t two = q.mode == LSMBLK_MERGE_TWO_LEVEL, newest = q.mode == LSMBLK_MERGE_NEWEST;
+  int rc = c->cws.grow(st, plan_merge(nullptr, n, nrun).bytes, 1);
   if (rc) return rc;
-  P = plan_merge(c->cws, n, nrun);
-  if (plan_out) *plan_out = P;
+  MergePlan P = plan_merge(c->cws, n, nrun);
+  if (q.plan_out) *q.plan_out = P;
   MergeArgs& m = P.m;
   m.keys = in->keys;
   m.key_off = in->key_off;
   m.n = n;
-  m.run_start = run_start;
+  m.run_start = q.run_start;
   m.nrun = nrun;
   m.two = two;
-  m.two_end = two_end;
+  m.two_end = q.two_end;
   m.ts = in->ts;
   m.newest = newest;
-  if (hipMemsetAsync(stats, 0, LSMBLK_STATS_WORDS * 8, st) != hipSuccess) return LSMBLK_E_HIP;
+  if (hipMemsetAsync(q.stats, 0, LSMBLK_STATS_WORDS * 8, st) != hipSuccess) return LSMBLK_E_HIP;
   if (n == 0) {
     LSM_LAUNCH(merge_empty_kernel, dim3(1), dim3(64), 0, st, m.mstats, out->key_off, out->val_off,
-                       out->entry_cap, stats);
-    return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
+                       out->entry_cap, q.stats);
+    return launch_rc();
   }
   if (hipMemsetAsync(m.mstats, 0, 64, st) != hipSuccess) return LSMBLK_E_HIP;
   const uint32_t nc = m.nc_max;
@@ -2101,7 +2096,7 @@ int merge_gather_locked(lsmblk_ctx* c, const lsmblk_kv_stream* in, const uint32_
   LSM_LAUNCH(tscan_part_kernel, dim3((nc + kTScan - 1) / kTScan), dim3(256), 0, st, m);
   LSM_LAUNCH(tscan_top_kernel, dim3(1), dim3(1024), 0, st, m);
   LSM_LAUNCH(perm_kernel, dim3(nc), dim3(64), 0, st, m);
-  if (hipGetLastError() != hipSuccess) return LSMBLK_E_HIP;
+  if (launch_rc()) return LSMBLK_E_HIP;
   GatherArgs g;
   g.keys = in->keys;
   g.key_off = in->key_off;
@@ -2113,11 +2108,11 @@ int merge_gather_locked(lsmblk_ctx* c, const lsmblk_kv_stream* in, const uint32_
   g.nm = m.mstats;
   g.n_max = n;
   g.rules = rules;
-  g.wm = wm;
-  g.bottom = bottom ? 1u : 0u;
-  g.npfx = npfx;
-  g.pfx = pfx;
-  g.pfx_off = pfx_off;
+  g.wm = rules ? q.rules->watermark : 0;
+  g.bottom = rules && q.rules->bottom_level ? 1u : 0u;
+  g.npfx = rules ? q.rules->nprefix : 0;
+  g.pfx = rules ? q.rules->prefixes : nullptr;
+  g.pfx_off = rules ? q.rules->prefix_off : nullptr;
   g.okeys = out->keys;
   g.okey_off = out->key_off;
   g.ovals = out->vals;
@@ -2131,32 +2126,32 @@ int merge_gather_locked(lsmblk_ctx* c, const lsmblk_kv_stream* in, const uint32_
   g.tile_pre = P.gtile + 3 * P.gtiles;
   g.part_sum = P.gtile + 6 * P.gtiles;
   g.part_pre = g.part_sum + 3 * (P.gtiles / kGScan + 2);
-  g.stats = stats;
+  g.stats = q.stats;
   g.merr = m.mstats + 3;
-  g.range = range ? *range : lsmblk_key_range{};
+  g.range = q.range ? *q.range : lsmblk_key_range{};
   g.two = two;
-  g.ksame = two && rules ? (ksame_out ? ksame_out : P.ksame) : nullptr;
+  g.ksame = two && rules ? (q.ksame_out ? q.ksame_out : P.ksame) : nullptr;
   const uint32_t gt = uint32_t((n + kGTile - 1) / kGTile);
   if (two && rules) LSM_LAUNCH(mgroup_kernel, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, st, g);
   LSM_LAUNCH(mflag_kernel, dim3(gt), dim3(256), 0, st, g);
   LSM_LAUNCH(mscan_part_kernel, dim3(uint32_t((P.gtiles + kGScan - 1) / kGScan)), dim3(256), 0, st, g);
   LSM_LAUNCH(mscan_top_kernel, dim3(1), dim3(1024), 0, st, g);
-  if (defer) {  // the metadata now (with kidx), the bytes by the caller (mwrite_bytes)
+  if (q.defer) {  // the metadata now (with kidx), the bytes by the caller (mwrite_bytes)
     g.kidx = P.kidx;
     LSM_LAUNCH_NAMED("mwrite_kernel<true,false>", mwrite_kernel<true, false>, dim3(gt), dim3(256), 0, st, g);
-    *defer = g;
+    *q.defer = g;
   } else {
     g.kidx = nullptr;
     LSM_LAUNCH_NAMED("mwrite_kernel<true,true>", mwrite_kernel<true, true>, dim3(gt), dim3(256), 0, st, g);
   }
-  return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
+  return launch_rc();
 }
 
 // The deferred half of merge_gather_locked: the kept entries' key and value bytes.
 int mwrite_bytes(const GatherArgs& g, uint64_t n, hipStream_t st) {
   if (n == 0) return LSMBLK_OK;
   LSM_LAUNCH_NAMED("mwrite_kernel<false,true>", mwrite_kernel<false, true>, dim3(uint32_t((n + kGTile - 1) / kGTile)), dim3(256), 0, st, g);
-  return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
+  return launch_rc();
 }
 
 __global__ void set_u64_kernel(uint64_t* p, uint64_t v) {
@@ -2256,7 +2251,23 @@ int rotation_chains(const RotArgs& r, hipStream_t st) {
   }
   if (kDiag && r.poison) LSM_LAUNCH(rot_poison_kernel, dim3(uint32_t((r.n_max / 3 + 256) / 256)), dim3(256), 0, st, r);
   LSM_LAUNCH(rot_f_kernel, dim3(uint32_t((r.n_max + 1 + 511) / 512)), dim3(256), 0, st, r);
-  return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
+  return launch_rc();
+}
+
+// The rotation of plan P over the stream kv (P.dn entries of it) into starts[0, sst_cap), stats to `stats`.
+RotArgs rot_args(const lsmblk_ctx* c, const RotPlan& P, const lsmblk_kv_stream* kv, uint32_t block_size,
+                 uint32_t* starts, uint32_t sst_cap, uint64_t* stats) {
+  RotArgs r = P.r;
+  r.keys = kv->keys;
+  r.key_off = kv->key_off;
+  r.val_off = kv->val_off;
+  r.dn = P.dn;
+  r.block_size = block_size;
+  r.starts = starts;
+  r.sst_cap = sst_cap;
+  r.stats = stats;
+  r.poison = c->rot_poison;
+  return r;
 }
 
 int rotation_locked(lsmblk_ctx* c, RotArgs r, hipStream_t st) {
@@ -2294,7 +2305,7 @@ int rotation_locked(lsmblk_ctx* c, RotArgs r, hipStream_t st) {
     nxt = cur == r.F1 ? r.F2 : r.F1;  // F (F0) is kept for the fill
   }
   LSM_LAUNCH(rot_finish_kernel, dim3(1), dim3(256), 0, st, r);
-  return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
+  return launch_rc();
 }
 
 // Final stats of lsmblk_compact_batch from the stage stats.
@@ -2371,18 +2382,25 @@ int lsmblk_compact_merge_batch_ex(lsmblk_ctx* c, const lsmblk_kv_stream* in, con
   if (two_end > LSMBLK_TWO_END_BELOW || (two && !kept_same)) return LSMBLK_E_INVAL;
   if (range && ((range->has_lo && range->lo_len && !range->lo) || (range->has_hi && range->hi_len && !range->hi)))
     return LSMBLK_E_INVAL;
-  std::lock_guard<std::mutex> g(c->mu);
-  DeviceGuard dg(c->device, c);
-  if (!dg.ok) return LSMBLK_E_HIP;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(stats + 4, 0, 8, st) != hipSuccess) return LSMBLK_E_HIP;
+  CallGuard call(c, stream, stats + 4, 1);  // (the merge zeroes the words before it)
+  if (call.rc) return call.rc;
   MergePlan MP{};
-  if ((rc = merge_gather_locked(c, in, run_start, nrun, 1, o->watermark, o->bottom_level, o->prefixes, o->prefix_off,
-                                o->nprefix, range, kept, stats, st, &MP, o->merge_mode, two_end,
-                                two ? kept_same : nullptr)))
-    return rc;
-  if (in->n) LSM_LAUNCH(copy_u64_kernel, dim3(1), dim3(64), 0, st, stats + 4, MP.m.mstats);
-  return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
+  MergeReq q;
+  q.st = call.st;
+  q.in = in;
+  q.run_start = run_start;
+  q.nrun = nrun;
+  q.mode = o->merge_mode;
+  q.rules = o;
+  q.range = range;
+  q.two_end = two_end;
+  q.out = kept;
+  q.stats = stats;
+  q.ksame_out = two ? kept_same : nullptr;
+  q.plan_out = &MP;
+  if ((rc = merge_gather_locked(c, q))) return rc;
+  if (in->n) LSM_LAUNCH(copy_u64_kernel, dim3(1), dim3(64), 0, call.st, stats + 4, MP.m.mstats);
+  return launch_rc();
 }
 
 int lsmblk_shard_rotation_prepare(lsmblk_ctx* c, const lsmblk_kv_stream* ext, uint64_t n_own, uint32_t flags,
@@ -2396,14 +2414,12 @@ int lsmblk_shard_rotation_prepare_ex(lsmblk_ctx* c, const lsmblk_kv_stream* ext,
   if (!c || !ext || !ext->key_off || !ext->val_off) return LSMBLK_E_INVAL;
   if (block_size == 0 || target_sst_size == 0 || sst_cap == 0 || n_own > ext->n || ext->n >= 0xFFFFFFF0ull)
     return LSMBLK_E_INVAL;
-  std::lock_guard<std::mutex> g(c->mu);
-  DeviceGuard dg(c->device, c);
-  if (!dg.ok) return LSMBLK_E_HIP;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  CallGuard call(c, stream);
+  if (call.rc) return call.rc;
+  hipStream_t st = call.st;
   c->shard_ready = false;
   const uint32_t fl = shard_flevels(sst_cap);
-  const RotPlan P0 = plan_rot(nullptr, 0, ext->n, target_sst_size, block_size, fl);
-  int rc = grow(st, &c->rws, &c->rws_cap, P0.bytes, 1);
+  int rc = c->rws.grow(st, plan_rot(nullptr, 0, ext->n, target_sst_size, block_size, fl).bytes, 1);
   if (rc) return rc;
   c->shard_n = ext->n;
   c->shard_m = n_own;
@@ -2418,21 +2434,19 @@ int lsmblk_shard_rotation_prepare_ex(lsmblk_ctx* c, const lsmblk_kv_stream* ext,
   if ((rc = rotation_chains(r, st))) return rc;
   const uint32_t gr = uint32_t((ext->n + 1 + 255) / 256);
   for (uint32_t k = 1; k < fl; ++k) LSM_LAUNCH(rot_flev_kernel, dim3(gr), dim3(256), 0, st, r, k);
-  if (hipGetLastError() != hipSuccess) return LSMBLK_E_HIP;
+  if (launch_rc()) return LSMBLK_E_HIP;
   c->shard_ready = true;
   return LSMBLK_OK;
 }
 
 int lsmblk_shard_rotation_carry(lsmblk_ctx* c, const uint64_t* carry_in, uint64_t* carry_out, void* stream) {
   if (!c || !carry_in || !carry_out) return LSMBLK_E_INVAL;
-  std::lock_guard<std::mutex> g(c->mu);
+  CallGuard call(c, stream);
   if (!c->shard_ready) return LSMBLK_E_INVAL;
-  DeviceGuard dg(c->device, c);
-  if (!dg.ok) return LSMBLK_E_HIP;
+  if (call.rc) return call.rc;
   const RotArgs r = shard_args(c, nullptr);
-  LSM_LAUNCH(shard_carry_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), r, carry_in,
-                     carry_out);
-  return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
+  LSM_LAUNCH(shard_carry_kernel, dim3(1), dim3(64), 0, call.st, r, carry_in, carry_out);
+  return launch_rc();
 }
 
 int lsmblk_shard_encode_batch(lsmblk_ctx* c, const lsmblk_kv_stream* ext, uint8_t* out, uint64_t out_cap,
@@ -2441,34 +2455,39 @@ int lsmblk_shard_encode_batch(lsmblk_ctx* c, const lsmblk_kv_stream* ext, uint8_
   if (!c || !ext || !ext->key_off || !ext->val_off || !out || !blk_off || !seg_start || !seg_blk || !stats)
     return LSMBLK_E_INVAL;
   if (seg_cap < 2 || blk_cap == 0 || (reinterpret_cast<uintptr_t>(out) & 15) != 0) return LSMBLK_E_INVAL;
-  std::lock_guard<std::mutex> g(c->mu);
+  CallGuard call(c, stream);  // (the stats are zeroed once the shard is known to be prepared)
   if (!c->shard_ready || ext->n != c->shard_n) return LSMBLK_E_INVAL;
-  DeviceGuard dg(c->device, c);
-  if (!dg.ok) return LSMBLK_E_HIP;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (call.rc) return call.rc;
+  hipStream_t st = call.st;
   const RotArgs r = shard_args(c, ext);
   uint64_t* est = r.sstate + 8;
   if (hipMemsetAsync(stats, 0, LSMBLK_COMPACT_STATS_WORDS * 8, st) != hipSuccess) return LSMBLK_E_HIP;
   if (hipMemsetAsync(blk_off, 0, 8, st) != hipSuccess) return LSMBLK_E_HIP;
   LSM_LAUNCH(shard_seg_kernel, dim3((seg_cap + 255) / 256), dim3(256), 0, st, r, seg_start, seg_cap, r.nsst);
-  if (hipGetLastError() != hipSuccess) return LSMBLK_E_HIP;
-  int rc = lsmblk_impl::encode_locked(c, ext, nullptr, seg_start, r.nsst, seg_cap - 1, c->shard_block_size, out,
-                                      out_cap, blk_off, blk_cap, est, st, true);
+  if (launch_rc()) return LSMBLK_E_HIP;
+  lsmblk_impl::EncodeReq q;
+  q.st = st;
+  q.in = ext;
+  q.seg_start = seg_start;
+  q.dnseg = r.nsst;
+  q.nseg = seg_cap - 1;
+  q.block_size = c->shard_block_size;
+  q.out = out;
+  q.out_cap = out_cap;
+  q.blk_off = blk_off;
+  q.blk_cap = blk_cap;
+  q.stats = est;
+  q.span = true;
+  int rc = lsmblk_impl::encode_locked(c, q);
   if (rc) return rc;
   if ((rc = lsmblk_impl::segment_blocks_locked(c, seg_start, seg_cap - 1, est, seg_blk, st))) return rc;
   LSM_LAUNCH(shard_stats_kernel, dim3(1), dim3(64), 0, st, stats, est, r.sstate);
-  return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
+  return launch_rc();
 }
 
 int lsmblk_merge_batch(lsmblk_ctx* c, const lsmblk_kv_stream* in, const uint32_t* run_start, uint32_t nrun,
                        const lsmblk_kv_stream* out, uint64_t* stats, void* stream) {
-  int rc = check_merge_args(c, in, run_start, nrun, out, stats);
-  if (rc) return rc;
-  std::lock_guard<std::mutex> g(c->mu);
-  DeviceGuard dg(c->device, c);
-  if (!dg.ok) return LSMBLK_E_HIP;
-  return merge_gather_locked(c, in, run_start, nrun, 0, 0, 0, nullptr, nullptr, 0, nullptr, out, stats,
-                             reinterpret_cast<hipStream_t>(stream), nullptr, LSMBLK_MERGE_RUNS);
+  return lsmblk_merge_batch_ex(c, in, run_start, nrun, LSMBLK_MERGE_RUNS, out, stats, stream);
 }
 
 int lsmblk_merge_batch_ex(lsmblk_ctx* c, const lsmblk_kv_stream* in, const uint32_t* run_start, uint32_t nrun,
@@ -2476,11 +2495,17 @@ int lsmblk_merge_batch_ex(lsmblk_ctx* c, const lsmblk_kv_stream* in, const uint3
   int rc = check_merge_args(c, in, run_start, nrun, out, stats);
   if (rc) return rc;
   if (merge_mode > LSMBLK_MERGE_NEWEST) return LSMBLK_E_INVAL;
-  std::lock_guard<std::mutex> g(c->mu);
-  DeviceGuard dg(c->device, c);
-  if (!dg.ok) return LSMBLK_E_HIP;
-  return merge_gather_locked(c, in, run_start, nrun, 0, 0, 0, nullptr, nullptr, 0, nullptr, out, stats,
-                             reinterpret_cast<hipStream_t>(stream), nullptr, merge_mode);
+  CallGuard call(c, stream);  // (the merge zeroes the stats)
+  if (call.rc) return call.rc;
+  MergeReq q;
+  q.st = call.st;
+  q.in = in;
+  q.run_start = run_start;
+  q.nrun = nrun;
+  q.mode = merge_mode;
+  q.out = out;
+  q.stats = stats;
+  return merge_gather_locked(c, q);
 }
 
 int lsmblk_sst_rotation_batch(lsmblk_ctx* c, const lsmblk_kv_stream* in, uint32_t block_size,
@@ -2488,27 +2513,14 @@ int lsmblk_sst_rotation_batch(lsmblk_ctx* c, const lsmblk_kv_stream* in, uint32_
                               void* stream) {
   if (!c || !in || !sst_start || !stats || !in->key_off || !in->val_off) return LSMBLK_E_INVAL;
   if (block_size == 0 || target_sst_size == 0 || sst_cap == 0 || in->n >= 0xFFFFFFF0ull) return LSMBLK_E_INVAL;
-  std::lock_guard<std::mutex> g(c->mu);
-  DeviceGuard dg(c->device, c);
-  if (!dg.ok) return LSMBLK_E_HIP;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  RotPlan P = plan_rot(nullptr, 0, in->n, target_sst_size, block_size);
-  int rc = ensure_ws(c, P.bytes, st);
+  CallGuard call(c, stream, stats, LSMBLK_STATS_WORDS);
+  if (call.rc) return call.rc;
+  hipStream_t st = call.st;
+  const int rc = c->cws.grow(st, plan_rot(nullptr, 0, in->n, target_sst_size, block_size).bytes, 1);
   if (rc) return rc;
-  P = plan_rot(c->cws, 0, in->n, target_sst_size, block_size);
-  if (hipMemsetAsync(stats, 0, LSMBLK_STATS_WORDS * 8, st) != hipSuccess) return LSMBLK_E_HIP;
+  const RotPlan P = plan_rot(c->cws, 0, in->n, target_sst_size, block_size);
   LSM_LAUNCH(set_u64_kernel, dim3(1), dim3(64), 0, st, P.dn, uint64_t(in->n));
-  RotArgs r = P.r;
-  r.keys = in->keys;
-  r.key_off = in->key_off;
-  r.val_off = in->val_off;
-  r.dn = P.dn;
-  r.block_size = block_size;
-  r.starts = sst_start;
-  r.sst_cap = sst_cap;
-  r.stats = stats;
-  r.poison = c->rot_poison;
-  return rotation_locked(c, r, st);
+  return rotation_locked(c, rot_args(c, P, in, block_size, sst_start, sst_cap, stats), st);
 }
 
 int lsmblk_compact_batch(lsmblk_ctx* c, const lsmblk_kv_stream* in, const uint32_t* run_start, uint32_t nrun,
@@ -2523,20 +2535,18 @@ int lsmblk_compact_batch(lsmblk_ctx* c, const lsmblk_kv_stream* in, const uint32
   if (o->merge_mode > LSMBLK_MERGE_NEWEST) return LSMBLK_E_INVAL;
   if ((reinterpret_cast<uintptr_t>(out) & 15) != 0) return LSMBLK_E_INVAL;
   const uint32_t two = o->merge_mode == LSMBLK_MERGE_TWO_LEVEL;
-  std::lock_guard<std::mutex> g(c->mu);
-  DeviceGuard dg(c->device, c);
-  if (!dg.ok) return LSMBLK_E_HIP;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  CallGuard call(c, stream, stats, LSMBLK_COMPACT_STATS_WORDS);
+  if (call.rc) return call.rc;
+  hipStream_t st = call.st;
   const uint64_t n = in->n;
   // workspace: merge + gather, then rotation, then the stage stats
-  MergePlan M = plan_merge(nullptr, n, nrun);
-  RotPlan R = plan_rot(nullptr, M.bytes, n, o->target_sst_size, o->block_size);
-  const uint64_t stats_off = (R.bytes + 255) & ~uint64_t(255);
-  if ((rc = ensure_ws(c, stats_off + 4 * 64, st))) return rc;
-  uint64_t* sts = reinterpret_cast<uint64_t*>(c->cws + stats_off);
+  const uint64_t merge_bytes = plan_merge(nullptr, n, nrun).bytes;
+  const uint64_t stats_off = plan_rot(nullptr, merge_bytes, n, o->target_sst_size, o->block_size).bytes;
+  if ((rc = c->cws.grow(st, stats_off + 4 * 64, 1))) return rc;
+  const RotPlan R = plan_rot(c->cws, merge_bytes, n, o->target_sst_size, o->block_size);
+  uint64_t* sts = Carve{c->cws, stats_off}.take<uint64_t>(32);
   uint64_t *fst = sts, *rst = sts + 8, *est = sts + 16;
   if (hipMemsetAsync(sts, 0, 4 * 64, st) != hipSuccess) return LSMBLK_E_HIP;
-  if (hipMemsetAsync(stats, 0, LSMBLK_COMPACT_STATS_WORDS * 8, st) != hipSuccess) return LSMBLK_E_HIP;
   if (hipMemsetAsync(blk_off, 0, 8, st) != hipSuccess) return LSMBLK_E_HIP;
   // The rotation needs only the kept entries' metadata (and their keys, read in the merge input
   // through kidx), so the kept stream's key and value bytes are gathered on `st` while the
@@ -2545,44 +2555,53 @@ int lsmblk_compact_batch(lsmblk_ctx* c, const lsmblk_kv_stream* in, const uint32
   // section 10.)
   MergePlan MP{};
   GatherArgs G{};
-  if ((rc = merge_gather_locked(c, in, run_start, nrun, 1, o->watermark, o->bottom_level, o->prefixes, o->prefix_off,
-                                o->nprefix, nullptr, kept, fst, st, &MP, o->merge_mode, LSMBLK_TWO_END_IN_RANGE, nullptr,
-                                &G)))
-    return rc;
-  R = plan_rot(c->cws, M.bytes, n, o->target_sst_size, o->block_size);
+  MergeReq mq;
+  mq.st = st;
+  mq.in = in;
+  mq.run_start = run_start;
+  mq.nrun = nrun;
+  mq.mode = o->merge_mode;
+  mq.rules = o;
+  mq.out = kept;
+  mq.stats = fst;
+  mq.plan_out = &MP;
+  mq.defer = &G;
+  if ((rc = merge_gather_locked(c, mq))) return rc;
   LSM_LAUNCH(gate_kernel, dim3(1), dim3(64), 0, st, fst, (const uint64_t*)(MP.m.mstats + 3), R.dn);
-  RotArgs r = R.r;
-  r.keys = kept->keys;
-  r.key_off = kept->key_off;
-  r.val_off = kept->val_off;
-  r.dn = R.dn;  // kept entries (0 after a merge / rules error)
-  r.block_size = o->block_size;
-  r.starts = sst_start;
-  r.sst_cap = sst_cap;
-  r.stats = rst;
+  RotArgs r = rot_args(c, R, kept, o->block_size, sst_start, sst_cap, rst);  // (R.dn: 0 after a merge / rules error)
   r.ksame = two ? MP.ksame : nullptr;
   r.kidx = MP.kidx;
   r.k16 = MP.m.k16;
   r.akeys = in->keys;
   r.akey_off = in->key_off;
   r.an = n;
-  r.poison = c->rot_poison;
-  if ((rc = lsmblk_impl::fork_aux(c, st))) return rc;
+  // (joined on every path once forked, ADVICE round 5: after an error the caller's stream still
+  // waits for the rotation work already queued on c->aux, which writes sst_start and the workspace)
+  if ((rc = call.fork())) return rc;
   rc = rotation_locked(c, r, c->aux);
   if (!rc) rc = mwrite_bytes(G, n, st);
-  // joined on every path once forked: after an error the caller's stream still
-  // waits for the rotation work already queued on c->aux, which writes sst_start and the workspace
-  const int jrc = lsmblk_impl::join_aux(c, st);
+  const int jrc = call.join();
   if (rc) return rc;
   if (jrc) return jrc;
   lsmblk_kv_stream ks = *kept;
   ks.n = n;  // bound; the encode reads the kept count from fst[0]
-  if ((rc = lsmblk_impl::encode_locked(c, &ks, R.dn, sst_start, r.nsst, sst_cap - 1, o->block_size, out, out_cap,
-                                       blk_off, blk_cap, est, st)))
-    return rc;
+  lsmblk_impl::EncodeReq eq;
+  eq.st = st;
+  eq.in = &ks;
+  eq.dn = R.dn;
+  eq.seg_start = sst_start;
+  eq.dnseg = r.nsst;
+  eq.nseg = sst_cap - 1;
+  eq.block_size = o->block_size;
+  eq.out = out;
+  eq.out_cap = out_cap;
+  eq.blk_off = blk_off;
+  eq.blk_cap = blk_cap;
+  eq.stats = est;
+  if ((rc = lsmblk_impl::encode_locked(c, eq))) return rc;
   if ((rc = lsmblk_impl::segment_blocks_locked(c, sst_start, sst_cap - 1, est, sst_blk, st))) return rc;
   LSM_LAUNCH(compact_stats_kernel, dim3(1), dim3(64), 0, st, stats, fst, rst, est, MP.m.mstats);
-  return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
+  return launch_rc();
 }
 
 }  // extern "C"

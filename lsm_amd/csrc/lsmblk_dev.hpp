@@ -853,40 +853,112 @@ constexpr uint32_t kDecLagDefault = 10240;
 constexpr uint64_t kDecLagBytesDefault = 10240ull * 4096;
 constexpr uint32_t kScanUnitsDefault = 1u << 17;
 
+// Look-back status granules live in uncached device memory: every poll and publish goes to
+// the coherence point, so no XCD's L2 can hold a stale copy (MI355X L2s are per XCD and not
+// coherent with each other).
+constexpr unsigned kStatusFlags = hipDeviceMallocUncached;
+
+// A workspace buffer of a context: grown on demand on the calling ABI call's stream, released
+// with the context.  A context's buffers chain themselves (lsmblk_ctx::bufs, DevBufBase::next), so
+// lsmblk_ctx_destroy releases them without naming them.
+//
+// Growth is ordered on the call's stream `st`:
+//   * the new buffer is zeroed by hipMemsetAsync on st, so the fill precedes every kernel the call
+//     launches on st (round 4's hang: a null-stream hipMemset, unordered with the caller's
+//     non-blocking stream, wiped a fresh context's rotation levels after they were written);
+//   * ordinary buffers come from the device's stream-ordered pool (hipMallocAsync) and the old one
+//     is released by hipFreeAsync on st, after the work queued before it on st -- a context's
+//     work is on its caller's stream, and every call that forks onto the context's second stream
+//     joins it back into st before returning (CallGuard::join, also on its error paths);
+//   * uncached status memory (hipExtMallocWithFlags) has no stream-ordered free: st is
+//     synchronized and hipFree releases it (hipFree synchronizes the device, as HIP documents it;
+//     status arrays grow only with the batch's block or segment count).
+// Round 5 zeroed with hipMemset + hipDeviceSynchronize, which stalled every context and stream of
+// the device whenever any context grew (ADVICE / VERDICT round 5).
+struct DevBufBase {
+  void* mem = nullptr;
+  uint64_t cap = 0;    // elements the buffer holds (0: none)
+  uint64_t bytes = 0;  // its size
+  const bool status;   // uncached status memory (kStatusFlags)
+  DevBufBase* next;
+  DevBufBase(DevBufBase*& chain, bool status_) : status(status_), next(chain) { chain = this; }
+  DevBufBase(const DevBufBase&) = delete;  // (a copy would not be on the chain)
+  ~DevBufBase() { release(); }
+  // Room for `need` elements of `elem` bytes (capacity need + need / 4 + 1024 when it grows).
+  // *fresh is set when the memory is new (and so all zero); it is never cleared.
+  int grow_bytes(hipStream_t st, uint64_t need, uint64_t elem, bool* fresh) {
+    if (need <= cap) return LSMBLK_OK;
+    const uint64_t nc = need + need / 4 + 1024, nb = nc * elem;
+    if (mem) {
+      if (status) {
+        if (hipStreamSynchronize(st) != hipSuccess) return LSMBLK_E_HIP;
+        (void)hipFree(mem);
+      } else if (hipFreeAsync(mem, st) != hipSuccess) {
+        return LSMBLK_E_HIP;
+      }
+      mem = nullptr;
+      cap = bytes = 0;
+    }
+    const hipError_t e = status ? hipExtMallocWithFlags(&mem, nb, kStatusFlags) : hipMallocAsync(&mem, nb, st);
+    if (e != hipSuccess) {
+      mem = nullptr;
+      return LSMBLK_E_NOMEM;
+    }
+    if (fresh) *fresh = true;
+    if (hipMemsetAsync(mem, 0, nb, st) != hipSuccess) return LSMBLK_E_HIP;
+    cap = nc;
+    bytes = nb;
+    return LSMBLK_OK;
+  }
+  // The whole buffer zeroed on st (nothing when there is none).
+  bool zero(hipStream_t st) const { return !bytes || hipMemsetAsync(mem, 0, bytes, st) == hipSuccess; }
+  // At context destruction (the device is synchronized by then; pool frees go to the null stream).
+  void release() {
+    if (!mem) return;
+    if (status) (void)hipFree(mem);
+    else (void)hipFreeAsync(mem, nullptr);
+    mem = nullptr;
+    cap = bytes = 0;
+  }
+};
+template <typename T>
+struct DevBuf : DevBufBase {
+  using DevBufBase::DevBufBase;
+  T* get() const { return static_cast<T*>(mem); }
+  operator T*() const { return get(); }
+  // `need` elements of `per` T each
+  int grow(hipStream_t st, uint64_t need, uint64_t per, bool* fresh = nullptr) {
+    return grow_bytes(st, need, per * sizeof(T), fresh);
+  }
+};
+
 struct lsmblk_ctx {
   int device = 0;
   std::mutex mu;
+  DevBufBase* bufs = nullptr;    // every DevBuf below
   uint32_t* counters = nullptr;  // [0] decode ticket, [1] plan ticket, [2] emit big-block count
-  uint32_t* dec_agg = nullptr;   // (entries, key bytes, value bytes) per block
-  uint64_t dec_cap = 0;
+  DevBuf<uint32_t> dec_agg{bufs, false};   // (entries, key bytes, value bytes) per block
   void* crc_tabs = nullptr;      // CrcTabs: CRC-32 slicing + zero-extension tables (first CRC call)
-  uint64_t* tile_sum = nullptr;  // 3 per 64-block tile
-  uint64_t* tile_pre = nullptr;
-  uint64_t tile_cap = 0;
-  uint64_t* seg_agg = nullptr;   // 2 granules per segment
-  uint64_t* seg_inc = nullptr;
-  uint64_t seg_cap = 0;
-  uint32_t* rec_first = nullptr; // n+1
-  uint32_t* blk_first = nullptr;
-  uint32_t* ent = nullptr;       // per (segment-local) block: its encoded size (plan walk)
-  uint32_t* big_list = nullptr;  // n+1 u32: emit_big_kernel's per-block flags (bytes)
-  uint32_t* blk_sz = nullptr;    // n+1: every block's size (per-segment slot output)
-  uint64_t rec_cap = 0;
+  DevBuf<uint64_t> tile_sum{bufs, false};  // 3 per 64-block tile
+  DevBuf<uint64_t> tile_pre{bufs, false};
+  DevBuf<uint64_t> seg_agg{bufs, true};    // 2 granules per segment
+  DevBuf<uint64_t> seg_inc{bufs, true};
+  DevBuf<uint32_t> rec_first{bufs, false}; // n+1
+  DevBuf<uint32_t> blk_first{bufs, false};
+  DevBuf<uint32_t> ent{bufs, false};       // per (segment-local) block: its encoded size (plan walk)
+  DevBuf<uint32_t> big_list{bufs, false};  // n+1 u32: emit_big_kernel's per-block flags (bytes)
+  DevBuf<uint32_t> blk_sz{bufs, false};    // n+1: every block's size (per-segment slot output)
   // fused walk + emit (encode_fused_kernel): 4 uncached granules per block record, R(w, i) < n +
   // walkers; per walker its block count (uncached granule, and plain); per record a big-block flag
-  uint64_t* frec = nullptr;
-  uint64_t frec_cap = 0;
-  uint64_t* fdone = nullptr;
-  uint64_t fdone_cap = 0;
-  uint32_t* fwnb = nullptr;
-  uint64_t fwnb_cap = 0;
-  uint8_t* fbig = nullptr;
-  uint64_t fbig_cap = 0;
+  DevBuf<uint64_t> frec{bufs, true};
+  DevBuf<uint64_t> fdone{bufs, true};
+  DevBuf<uint32_t> fwnb{bufs, false};
+  DevBuf<uint8_t> fbig{bufs, false};
   bool fuse_on = false;          // diagnostics: slot output through encode_fused_kernel (A/B)
   bool plan_pipe = false;        // the plan walk's helper pipelined over chunks (LSMBLK_DEBUG_PLAN_PIPE, A/B)
   uint32_t emit_mode = 0;        // LSMBLK_DEBUG_EMIT_MODE: 0 default, 1 emit_kernel, 2 emit_block_kernel (A/B)
   uint32_t emit_grid = 0;        // emit_block_kernel's grid clamp (0: kEmitGridMax; tests reach its block loop)
-  uint64_t* lag_gran = nullptr;  // lagged decode granules (uncached): 3 aggregate + 3 base per block,
+  DevBuf<uint64_t> lag_gran{bufs, true};   // lagged decode granules: 3 aggregate + 3 base per block,
   uint64_t lag_blk_cap = 0;      //   then 3 aggregate + 3 inclusive per 64-block tile; blocks covered
   uint32_t rot_poison = 0;       // diagnostics builds only: LSMBLK_DEBUG_ROT_POISON
   uint32_t emit_poison = 0;      // diagnostics builds only: LSMBLK_DEBUG_EMIT_POISON
@@ -911,98 +983,34 @@ struct lsmblk_ctx {
   uint64_t klog_total = 0;       // launches logged since timing was switched on
   uint64_t dec_log0 = 0, dec_log1 = 0, enc_log0 = 0, enc_log1 = 0;  // klog_total range of the last decode / encode
   // BlockMeta sections (lsmblk_block_meta_batch)
-  uint32_t* meta_rec = nullptr;     // nblk
-  uint64_t* meta_pos = nullptr;     // nblk + 1
-  uint64_t meta_blk_cap = 0;
-  uint64_t* meta_tile = nullptr;    // 2 per tile: sums, prefixes
-  uint64_t meta_tile_cap = 0;
-  uint32_t* meta_crc = nullptr;     // nseg
-  uint64_t meta_seg_cap = 0;
+  DevBuf<uint32_t> meta_rec{bufs, false};   // nblk
+  DevBuf<uint64_t> meta_pos{bufs, false};   // nblk + 1
+  DevBuf<uint64_t> meta_tile{bufs, false};  // 2 per tile: sums, prefixes
+  DevBuf<uint32_t> meta_crc{bufs, false};   // nseg
   uint64_t* meta_cstats = nullptr;  // crc_kernel stats of the section CRC pass
   // compaction filter (lsmblk_compact_filter_batch)
-  uint32_t* filt_keep = nullptr;    // n
-  uint64_t filt_cap = 0;
-  uint64_t* filt_tile = nullptr;    // 6 per tile: sums, prefixes
-  uint64_t filt_tile_cap = 0;
+  DevBuf<uint32_t> filt_keep{bufs, false};  // n
+  DevBuf<uint64_t> filt_tile{bufs, false};  // 6 per tile: sums, prefixes
   // merge / compaction pipeline (lsmblk_compact.hip): one arena, carved per call
-  uint8_t* cws = nullptr;
-  uint64_t cws_cap = 0;
+  DevBuf<uint8_t> cws{bufs, false};
   // CRC-verified decode (lsmblk_decode_batch_ex): per-block CRCs
-  uint32_t* vcrc = nullptr;
-  uint64_t vcrc_cap = 0;
+  DevBuf<uint32_t> vcrc{bufs, false};
   // lsmblk_compact_batch: a second stream for the SST rotation beside the kept stream's byte
   // gather, and the fork / join events (created on first use)
   hipStream_t aux = nullptr;
   hipEvent_t fork_ev = nullptr, join_ev = nullptr;
   // SST files (lsmblk_sst.hip)
-  uint8_t* sws = nullptr;
-  uint64_t sws_cap = 0;
+  DevBuf<uint8_t> sws{bufs, false};
   // range scans (lsmblk_sst_scan_batch): the work units a batch's blocks are spread over beyond
   // one per range (LSMBLK_DEBUG_SCAN_UNITS); the workspace is carved from sws
   uint32_t scan_units = kScanUnitsDefault;
   // key-range shard rotation (lsmblk_shard_*): its own arena, carved from the parameters of the
   // last lsmblk_shard_rotation_prepare, which the carry and encode calls replay
-  uint8_t* rws = nullptr;
-  uint64_t rws_cap = 0;
+  DevBuf<uint8_t> rws{bufs, false};
   uint64_t shard_n = 0, shard_m = 0, shard_target = 0;
   uint32_t shard_block_size = 0, shard_flags = 0, shard_sst_cap = 0;
   bool shard_ready = false;
 };
-
-namespace {
-
-// Look-back status granules live in uncached device memory: every poll and publish goes to
-// the coherence point, so no XCD's L2 can hold a stale copy (MI355X L2s are per XCD and not
-// coherent with each other).
-constexpr unsigned kStatusFlags = hipDeviceMallocUncached;
-
-// Workspace growth, ordered on the calling ABI call's stream `st`:
-//   * the new buffer is zeroed by hipMemsetAsync on st, so the fill precedes every kernel the call
-//     launches on st (round 4's hang: a null-stream hipMemset, unordered with the caller's
-//     non-blocking stream, wiped a fresh context's rotation levels after they were written);
-//   * ordinary buffers come from the device's stream-ordered pool (hipMallocAsync) and the old one
-//     is released by hipFreeAsync on st, after the work queued before it on st -- a context's
-//     work is on its caller's stream, and every call that forks onto the context's second stream
-//     joins it back into st before returning (join_aux, also on its error paths);
-//   * uncached status memory (hipExtMallocWithFlags) has no stream-ordered free: st is
-//     synchronized and hipFree releases it (hipFree synchronizes the device, as HIP documents it;
-//     status arrays grow only with the batch's block or segment count).
-// Round 5 zeroed with hipMemset + hipDeviceSynchronize, which stalled every context and stream of
-// the device whenever any context grew (ADVICE / VERDICT round 5).
-template <typename T>
-int grow(hipStream_t st, T** p, uint64_t* cap, uint64_t need, uint64_t per, unsigned flags = 0) {
-  if (need <= *cap) return LSMBLK_OK;
-  const uint64_t nc = need + need / 4 + 1024, bytes = nc * per * sizeof(T);
-  if (*p) {
-    if (flags) {
-      if (hipStreamSynchronize(st) != hipSuccess) return LSMBLK_E_HIP;
-      (void)hipFree(*p);
-    } else if (hipFreeAsync(*p, st) != hipSuccess) {
-      return LSMBLK_E_HIP;
-    }
-    *p = nullptr;
-    *cap = 0;
-  }
-  const hipError_t e = flags ? hipExtMallocWithFlags(reinterpret_cast<void**>(p), bytes, flags)
-                            : hipMallocAsync(reinterpret_cast<void**>(p), bytes, st);
-  if (e != hipSuccess) {
-    *p = nullptr;
-    *cap = 0;
-    return LSMBLK_E_NOMEM;
-  }
-  if (hipMemsetAsync(*p, 0, bytes, st) != hipSuccess) return LSMBLK_E_HIP;
-  *cap = nc;
-  return LSMBLK_OK;
-}
-// Release a buffer of grow() at context destruction (the device is synchronized by then).
-template <typename T>
-void release(T*& p, unsigned flags = 0) {
-  if (!p) return;
-  if (flags) (void)hipFree(p);
-  else (void)hipFreeAsync(p, nullptr);
-  p = nullptr;
-}
-}  // namespace
 
 // The context whose ABI call is running on this thread (set by DeviceGuard under the context's
 // lock): every kernel launch of the call goes through lsm_launch, which logs it when the
@@ -1085,14 +1093,28 @@ inline void lsm_launch(const char* name, int slot, K kern, dim3 grid, dim3 block
 
 // Internal entry points shared between translation units (called with ctx->mu held).
 namespace lsmblk_impl {
-// lsmblk_encode_batch with optional device-side entry count (dn) and segment count (dnseg):
-// in->n and nseg are then upper bounds that size the grids and the workspace.  span: the
-// segments cover [seg_start[0], seg_start[nseg]) of the stream (a key-range shard's part of a
-// stream that also holds the previous rank's crossing block and the halo), not all of it.
-int encode_locked(lsmblk_ctx* c, const lsmblk_kv_stream* in, const uint64_t* dn, const uint32_t* seg_start,
-                  const uint32_t* dnseg, uint32_t nseg, uint32_t block_size, uint8_t* out, uint64_t out_cap,
-                  uint64_t* blk_off, uint64_t blk_cap, uint64_t* stats, hipStream_t st, bool span = false,
-                  uint32_t flags = 0, uint64_t* seg_out = nullptr);
+// lsmblk_encode_batch_ex's arguments, with optional device-side entry count (dn) and segment
+// count (dnseg): in->n and nseg are then upper bounds that size the grids and the workspace.
+// span: the segments cover [seg_start[0], seg_start[nseg]) of the stream (a key-range shard's part
+// of a stream that also holds the previous rank's crossing block and the halo), not all of it.
+struct EncodeReq {
+  hipStream_t st = nullptr;
+  const lsmblk_kv_stream* in = nullptr;
+  const uint64_t* dn = nullptr;
+  const uint32_t* seg_start = nullptr;
+  const uint32_t* dnseg = nullptr;
+  uint32_t nseg = 0;
+  uint32_t block_size = 0;
+  uint8_t* out = nullptr;
+  uint64_t out_cap = 0;
+  uint64_t* blk_off = nullptr;
+  uint64_t blk_cap = 0;
+  uint64_t* stats = nullptr;
+  bool span = false;
+  uint32_t flags = 0;
+  uint64_t* seg_out = nullptr;
+};
+int encode_locked(lsmblk_ctx* c, const EncodeReq& q);
 // lsmblk_encode_segment_blocks for the encode that just ran on this context.
 int segment_blocks_locked(lsmblk_ctx* c, const uint32_t* seg_start, uint32_t nseg_max, const uint64_t* enc_stats,
                           uint32_t* seg_blk, hipStream_t st);
@@ -1116,3 +1138,61 @@ int block_meta_locked(lsmblk_ctx* c, const uint8_t* blocks, const uint64_t* blk_
                       const uint32_t* seg_blk, uint32_t nseg, uint8_t* meta, uint64_t meta_cap, uint64_t* meta_off,
                       uint64_t* stats, hipStream_t st);
 }  // namespace lsmblk_impl
+
+// ---------------------------------------------------------------- host: what the entry points share
+namespace {
+// A call's epilogue: whether every launch since the last look was accepted.
+inline int launch_rc() { return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP; }
+
+// A call's prologue: the context's lock, its device made current, the caller's stream, the stats
+// words (when given) zeroed on it.  rc != 0: the call returns it.  The arguments are validated
+// before the guard is built, which dereferences c.  A call that forks onto the context's second
+// stream does so through fork(): whatever path it then returns by, the caller's stream has waited
+// for the work queued there (join(), at the latest when the guard goes).
+struct CallGuard {
+  std::lock_guard<std::mutex> lock;
+  DeviceGuard dg;
+  lsmblk_ctx* const c;
+  hipStream_t st;
+  int rc;
+  bool forked = false;
+  CallGuard(lsmblk_ctx* c_, void* stream, uint64_t* stats = nullptr, uint32_t words = 0)
+      : lock(c_->mu), dg(c_->device, c_), c(c_), st(reinterpret_cast<hipStream_t>(stream)),
+        rc(dg.ok && (!stats || !words || hipMemsetAsync(stats, 0, words * 8, st) == hipSuccess) ? LSMBLK_OK
+                                                                                                  : LSMBLK_E_HIP) {}
+  ~CallGuard() { (void)join(); }
+  int fork() {
+    const int r = lsmblk_impl::fork_aux(c, st);
+    forked = r == LSMBLK_OK;
+    return r;
+  }
+  int join() {
+    if (!forked) return LSMBLK_OK;
+    forked = false;
+    return lsmblk_impl::join_aux(c, st);
+  }
+};
+
+// Workspace regions of an arena one after another, each rounded up to 256 bytes; off: their total.
+// A layout is a function of a Carve, run with a null base to measure and again on the arena to bind.
+struct Carve {
+  uint8_t* base;
+  uint64_t off = 0;
+  Carve(uint8_t* b, uint64_t o = 0) : base(b), off(o) {}
+  template <typename T>
+  T* take(uint64_t count) {
+    T* p = reinterpret_cast<T*>(base + off);
+    off = (off + count * sizeof(T) + 255) & ~uint64_t(255);
+    return p;
+  }
+};
+
+// Workgroups of `kern` (at `threads` threads, no dynamic LDS) resident at once on a device of `cus`
+// compute units, `per_cu` a CU when the runtime cannot say: the grid of a persistent kernel.
+template <typename K>
+inline uint32_t resident_wgs(int cus, K kern, int threads, int per_cu) {
+  int n = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, threads, 0) != hipSuccess || n < 1) n = per_cu;
+  return uint32_t(cus > 0 ? cus : 256) * uint32_t(n);
+}
+}  // namespace

@@ -1988,18 +1988,6 @@ bool bad_stream(const lsmblk_kv_stream* s) {  // (an absent stream is fine)
 }
 ViewArgs view_args(const lsmblk_lsm_view* v) { return ViewArgs{v->l0, v->nl0, v->nlevel, v->level_sst, v->level_start}; }
 
-// A call's prologue: the context's lock, its device made current, the caller's stream, the stats
-// words zeroed on it.  rc != 0: the call returns it.
-struct CallGuard {
-  std::lock_guard<std::mutex> lock;
-  DeviceGuard dg;
-  hipStream_t st;
-  int rc;
-  CallGuard(lsmblk_ctx* c, void* stream, uint64_t* stats, uint32_t words)
-      : lock(c->mu), dg(c->device, c), st(reinterpret_cast<hipStream_t>(stream)),
-        rc(dg.ok && hipMemsetAsync(stats, 0, words * 8, st) == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP) {}
-};
-
 // The first entry of an offsets array (or of both of a stream's) zeroed: an empty batch's result.
 bool zero_first(uint32_t* off, hipStream_t st) { return !off || hipMemsetAsync(off, 0, 4, st) == hipSuccess; }
 bool zero_first(const lsmblk_kv_stream* s, hipStream_t st) { return !s || (zero_first(s->key_off, st) && zero_first(s->val_off, st)); }
@@ -2017,24 +2005,67 @@ struct GridCap {
   }
 };
 
-// Workspace regions one after another, each rounded up to 256 bytes: the region's offset.
-struct Carve {
-  uint64_t need = 0;
-  uint64_t operator()(uint64_t bytes) {
-    const uint64_t o = need;
-    need += (bytes + 255) & ~255ull;
-    return o;
-  }
+// lsmblk_sst_open_batch's workspace: the CRC range table, the CRCs, the CRC pass's own stats.
+struct OpenWs {
+  uint64_t* tab;
+  uint32_t* crc;
+  uint64_t* cstats;
+  uint64_t bytes;
 };
+OpenWs open_ws(uint8_t* base, uint64_t nsst) {
+  Carve cv{base};
+  OpenWs w;
+  w.tab = cv.take<uint64_t>(4 * nsst + 1);
+  w.crc = cv.take<uint32_t>(4 * nsst);
+  w.cstats = cv.take<uint64_t>(32);
+  w.bytes = cv.off;
+  return w;
+}
 
-// The scan kernels' workspace: four regions of W and the unit budget.
-void scan_workspace(ScanArgs& a, uint8_t* W, uint64_t o_ubase, uint64_t o_qbad, uint64_t o_hdr, uint64_t o_cnt,
-                    uint64_t budget) {
-  a.ubase = reinterpret_cast<uint32_t*>(W + o_ubase);
-  a.qbad = reinterpret_cast<uint32_t*>(W + o_qbad);
-  a.hdr = reinterpret_cast<uint64_t*>(W + o_hdr);
-  a.ucnt = reinterpret_cast<uint64_t*>(W + o_cnt);
+// The scan kernels' workspace for nq scans spread over nq + budget units: ubase | qbad | hdr | ucnt.
+void scan_regions(Carve& cv, ScanArgs& a, uint64_t nq, uint64_t budget) {
+  a.ubase = cv.take<uint32_t>(nq + 1);
+  a.qbad = cv.take<uint32_t>(nq);
+  a.hdr = cv.take<uint64_t>(32);
+  a.ucnt = cv.take<uint64_t>(3 * (nq + budget));
   a.budget = uint32_t(budget);
+}
+// lsmblk_sst_scan_batch's workspace, sized by nq and the unit budget alone: a's regions; its size.
+uint64_t scan_ws(uint8_t* base, ScanArgs& a, uint64_t nq, uint64_t budget) {
+  Carve cv{base};
+  scan_regions(cv, a, nq, budget);
+  return cv.off;
+}
+
+// lsmblk_lsm_scan_batch's workspace, sized by nq, sub_cap, the unit budget and raw's entry capacity
+// alone: the regions of a and of the table scans s (s.qbad is a.sbad), and
+//   head (vflag, nsub, the table scans' stats) | pbad | mcnt | scnt | sbase | sub_q | sub_sst | sseg | table scan
+//   results | the scan kernels' ubase | qbad | hdr | ucnt | slot | opre
+struct LsmScanWs {
+  uint64_t* head;
+  lsmblk_scan_result* sres;
+  uint64_t zero_end;  // head, pbad and mcnt start from zero
+  uint64_t bytes;
+};
+LsmScanWs lsm_scan_ws(uint8_t* base, LsmScanArgs& a, ScanArgs& s, uint64_t budget) {
+  Carve cv{base};
+  LsmScanWs w;
+  w.head = cv.take<uint64_t>(32);
+  a.pbad = cv.take<uint32_t>(a.nq);
+  a.mcnt = cv.take<uint32_t>(a.nq);
+  w.zero_end = cv.off;
+  a.scnt = cv.take<uint32_t>(a.nq);
+  a.sbase = cv.take<uint32_t>(a.nq + 1);
+  a.sub_q = cv.take<uint32_t>(a.sub_cap);
+  a.sub_sst = cv.take<uint32_t>(a.sub_cap);
+  a.sseg = cv.take<uint32_t>(a.sub_cap + 1);
+  w.sres = cv.take<lsmblk_scan_result>(a.sub_cap);
+  scan_regions(cv, s, a.sub_cap, budget);
+  a.sbad = s.qbad;
+  a.slot = cv.take<uint32_t>(a.slot_cap);
+  a.opre = cv.take<uint32_t>(a.slot_cap + 1);
+  w.bytes = cv.off;
+  return w;
 }
 
 // The values of a point-read call's FOUND lookups: their offsets, then the bytes.
@@ -2060,19 +2091,15 @@ int lsmblk_sst_open_batch(lsmblk_ctx* c, const uint8_t* files, const uint64_t* f
   if (nsst == 0) return LSMBLK_OK;
   int rc;
   if ((rc = lsmblk_impl::ensure_crc_tabs(c, st))) return rc;
-  // workspace: the CRC range table, the CRCs, the CRC pass's own stats
-  Carve ws;
-  const uint64_t o_tab = ws(8ull * (4ull * nsst + 1)), o_crc = ws(16ull * nsst), o_cstats = ws(256);
-  if (ws.need > c->sws_cap && (rc = grow(st, &c->sws, &c->sws_cap, ws.need, 1))) return rc;
-  uint32_t* crc = reinterpret_cast<uint32_t*>(c->sws + o_crc);
-  uint64_t* cstats = reinterpret_cast<uint64_t*>(c->sws + o_cstats);
-  const OpenArgs a{files, file_off, nsst, desc, index, index_cap, reinterpret_cast<uint64_t*>(c->sws + o_tab), crc, stats};
-  if (hipMemsetAsync(cstats, 0, 32, st) != hipSuccess) return LSMBLK_E_HIP;
+  if ((rc = c->sws.grow(st, open_ws(nullptr, nsst).bytes, 1))) return rc;
+  const OpenWs w = open_ws(c->sws, nsst);
+  const OpenArgs a{files, file_off, nsst, desc, index, index_cap, w.tab, w.crc, stats};
+  if (hipMemsetAsync(w.cstats, 0, 32, st) != hipSuccess) return LSMBLK_E_HIP;
   LSM_LAUNCH(sst_open_prep_kernel, dim3(1), dim3(1024), 0, st, a);
   // (the ranges between the sections are flagged in cstats, which nothing reads)
-  if ((rc = lsmblk_impl::launch_crc(c, files, a.tab, 4ull * nsst, 0, crc, cstats, st, nullptr, true))) return rc;
+  if ((rc = lsmblk_impl::launch_crc(c, files, a.tab, 4ull * nsst, 0, w.crc, w.cstats, st, nullptr, true))) return rc;
   LSM_LAUNCH(sst_open_walk_kernel, dim3(nsst), dim3(64), 0, st, a);
-  return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
+  return launch_rc();
 }
 
 int lsmblk_sst_get_batch(lsmblk_ctx* c, const uint8_t* files, const uint64_t* file_off, uint32_t nsst,
@@ -2092,7 +2119,7 @@ int lsmblk_sst_get_batch(lsmblk_ctx* c, const uint8_t* files, const uint64_t* fi
   const GridCap grid(c);
   LSM_LAUNCH(sst_get_kernel, dim3(grid(nq, kGetWaves)), dim3(64 * kGetWaves), 0, st, a);
   if (vals) launch_values(a, grid, st);
-  return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
+  return launch_rc();
 }
 
 int lsmblk_lsm_get_batch(lsmblk_ctx* c, const uint8_t* files, const uint64_t* file_off, uint32_t nsst,
@@ -2110,17 +2137,17 @@ int lsmblk_lsm_get_batch(lsmblk_ctx* c, const uint8_t* files, const uint64_t* fi
   hipStream_t st = call.st;
   if (nq == 0) return !vals || zero_first(val_off, st) ? LSMBLK_OK : LSMBLK_E_HIP;
   int rc;
-  if (256 > c->sws_cap && (rc = grow(st, &c->sws, &c->sws_cap, 256, 1))) return rc;
+  if ((rc = c->sws.grow(st, 256, 1))) return rc;
   if (hipMemsetAsync(c->sws, 0, 256, st) != hipSuccess) return LSMBLK_E_HIP;
   const ViewArgs v = view_args(view);
-  uint32_t* const vflag = reinterpret_cast<uint32_t*>(c->sws);
+  uint32_t* const vflag = Carve{c->sws}.take<uint32_t>(64);
   const LsmGetArgs a{o, v, {qkeys, qkey_off, q_ts, nq, flags, vals, val_cap, val_off, stats}, res, vflag};
   const ViewCheckArgs vc{o, v, stats, vflag};
   const GridCap grid(c);
   LSM_LAUNCH(lsm_view_check_kernel, dim3(32), dim3(256), 0, st, vc);
   LSM_LAUNCH(lsm_get_kernel, dim3(grid(nq, kGetWaves)), dim3(64 * kGetWaves), 0, st, a);
   if (vals) launch_values(a, grid, st);
-  return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
+  return launch_rc();
 }
 
 int lsmblk_sst_scan_batch(lsmblk_ctx* c, const uint8_t* files, const uint64_t* file_off, uint32_t nsst,
@@ -2136,18 +2163,14 @@ int lsmblk_sst_scan_batch(lsmblk_ctx* c, const uint8_t* files, const uint64_t* f
   if (call.rc) return call.rc;
   hipStream_t st = call.st;
   if (nq == 0) return zero_first(seg_start, st) && zero_first(out, st) ? LSMBLK_OK : LSMBLK_E_HIP;
-  // workspace: ubase | qbad | hdr | ucnt, sized by nq and the unit budget alone
-  const uint64_t budget = c->scan_units, units = nq + budget;
-  Carve ws;
-  const uint64_t o_ubase = ws(4 * (nq + 1)), o_qbad = ws(4 * nq), o_hdr = ws(256);
-  const uint64_t o_cnt = ws.need, need = o_cnt + 24 * units;  // (the last region: not rounded up)
-  int rc;
-  if (need > c->sws_cap && (rc = grow(st, &c->sws, &c->sws_cap, need, 1))) return rc;
+  const uint64_t budget = c->scan_units;
   ScanArgs a{o, {lkeys, lkey_off, ukeys, ukey_off, q_bound}, q_sst, nq, flags, res, dev_stream(out), seg_start, stats};
-  scan_workspace(a, c->sws, o_ubase, o_qbad, o_hdr, o_cnt, budget);
+  int rc;
+  if ((rc = c->sws.grow(st, scan_ws(nullptr, a, nq, budget), 1))) return rc;
+  scan_ws(c->sws, a, nq, budget);
   const GridCap grid(c);
-  launch_scan<false>(a, grid(nq, kGetWaves), grid(units, kGetWaves), out != nullptr, st);
-  return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
+  launch_scan<false>(a, grid(nq, kGetWaves), grid(nq + budget, kGetWaves), out != nullptr, st);
+  return launch_rc();
 }
 
 int lsmblk_lsm_scan_batch(lsmblk_ctx* c, const uint8_t* files, const uint64_t* file_off, uint32_t nsst,
@@ -2167,52 +2190,32 @@ int lsmblk_lsm_scan_batch(lsmblk_ctx* c, const uint8_t* files, const uint64_t* f
   if (call.rc) return call.rc;
   hipStream_t st = call.st;
   if (nq == 0) return zero_first(seg_start, st) && zero_first(raw, st) && zero_first(out, st) ? LSMBLK_OK : LSMBLK_E_HIP;
-  // workspace, sized by nq, sub_cap, the unit budget and raw's entry capacity alone:
-  //   head (vflag, nsub, the table scans' stats) | pbad | mcnt | scnt | sbase | sub_q | sub_sst | sseg | table scan
-  //   results | the scan kernels' ubase | qbad | hdr | ucnt | slot | opre
   const uint64_t budget = c->scan_units, units = sub_cap + budget;
   const uint64_t slot_cap = raw ? (raw->entry_cap < 0xFFFFFFFFull ? raw->entry_cap : 0xFFFFFFFFull) : 0;
-  Carve carve;
-  const uint64_t o_head = carve(256), o_pbad = carve(4 * nq), o_mcnt = carve(4 * nq), zero_end = carve.need;
-  const uint64_t o_scnt = carve(4 * nq), o_sbase = carve(4 * (nq + 1)), o_subq = carve(4 * sub_cap), o_subs = carve(4 * sub_cap);
-  const uint64_t o_sseg = carve(4 * (sub_cap + 1)), o_sres = carve(sizeof(lsmblk_scan_result) * sub_cap);
-  const uint64_t o_ubase = carve(4 * (sub_cap + 1)), o_qbad = carve(4 * sub_cap), o_hdr = carve(256), o_cnt = carve(24 * units);
-  const uint64_t o_slot = carve(4 * slot_cap), o_opre = carve(4 * (slot_cap + 1));
-  int rc;
-  if (carve.need > c->sws_cap && (rc = grow(st, &c->sws, &c->sws_cap, carve.need, 1))) return rc;
-  uint8_t* const W = c->sws;
-  if (hipMemsetAsync(W, 0, zero_end, st) != hipSuccess) return LSMBLK_E_HIP;
-  // (a slot no entry ranks to -- only files that are not in key order leave one -- keeps nothing)
-  if (slot_cap && hipMemsetAsync(W + o_slot, 0, 4 * slot_cap, st) != hipSuccess) return LSMBLK_E_HIP;
-  auto u32p = [&](uint64_t o) { return reinterpret_cast<uint32_t*>(W + o); };
-  uint64_t* const head = reinterpret_cast<uint64_t*>(W + o_head);
 
   // the three argument structs, from the same opened set, view and bounds
   const ViewArgs v = view_args(view);
   const BoundArgs b{lkeys, lkey_off, ukeys, ukey_off, q_bound};
-  const ViewCheckArgs vc{o, v, stats, u32p(o_head)};
-
   LsmScanArgs a{o, v, b, q_ts, nq, sub_cap, res, dev_stream(raw), dev_stream(out), seg_start, stats};
-  a.vflag = vc.vflag;
-  a.nsub = head + 1;
-  a.sstats = head + 4;
-  a.pbad = u32p(o_pbad);
-  a.mcnt = u32p(o_mcnt);
-  a.scnt = u32p(o_scnt);
-  a.sbase = u32p(o_sbase);
-  a.sub_q = u32p(o_subq);
-  a.sub_sst = u32p(o_subs);
-  a.sseg = u32p(o_sseg);
-  a.sbad = u32p(o_qbad);
-  a.slot = u32p(o_slot);
-  a.opre = u32p(o_opre);
   a.slot_cap = slot_cap;
-
   // the table scans: range_overlap already passed (NO_FILTER), bounds and kinds of the scan's range
   // (their count is on the device: nq_dev; the output stream is raw, its runs' starts sseg)
-  ScanArgs s{o, b, a.sub_sst, 0, (newest ? LSMBLK_SCAN_MVCC : flags) | LSMBLK_SCAN_NO_FILTER,
-             reinterpret_cast<lsmblk_scan_result*>(W + o_sres), a.raw, a.sseg, a.sstats};
-  scan_workspace(s, W, o_ubase, o_qbad, o_hdr, o_cnt, budget);
+  ScanArgs s{o, b, nullptr, 0, (newest ? LSMBLK_SCAN_MVCC : flags) | LSMBLK_SCAN_NO_FILTER, nullptr, a.raw};
+
+  int rc;
+  if ((rc = c->sws.grow(st, lsm_scan_ws(nullptr, a, s, budget).bytes, 1))) return rc;
+  const LsmScanWs w = lsm_scan_ws(c->sws, a, s, budget);
+  if (hipMemsetAsync(c->sws, 0, w.zero_end, st) != hipSuccess) return LSMBLK_E_HIP;
+  // (a slot no entry ranks to -- only files that are not in key order leave one -- keeps nothing)
+  if (slot_cap && hipMemsetAsync(a.slot, 0, 4 * slot_cap, st) != hipSuccess) return LSMBLK_E_HIP;
+  a.vflag = reinterpret_cast<uint32_t*>(w.head);
+  a.nsub = w.head + 1;
+  a.sstats = w.head + 4;
+  const ViewCheckArgs vc{o, v, stats, a.vflag};
+  s.q_sst = a.sub_sst;
+  s.res = w.sres;
+  s.seg_start = a.sseg;
+  s.stats = a.sstats;
   s.nq_dev = a.nsub;
   s.parent = a.sub_q;
 
@@ -2230,7 +2233,7 @@ int lsmblk_lsm_scan_batch(lsmblk_ctx* c, const uint8_t* files, const uint64_t* f
     LSM_LAUNCH_NAMED("lsm_scan_rank_kernel", lsm_scan_rank_kernel<false>, dim3(grid(slot_cap, 256)), dim3(256), 0, st, a);
   LSM_LAUNCH(lsm_scan_offsets_kernel, dim3(1), dim3(kScanWg), 0, st, a);
   if (out) LSM_LAUNCH(lsm_scan_gather_kernel, dim3(grid(slot_cap, 16)), dim3(256), 0, st, a);
-  return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
+  return launch_rc();
 }
 
 }  // extern "C"

@@ -4100,65 +4100,34 @@ uint64_t lag_words(uint64_t nb) { return 6 * nb + 6 * ((nb + kTile - 1) / kTile 
 
 int reserve_locked(lsmblk_ctx* c, uint64_t blocks, uint64_t entries, uint64_t segs, hipStream_t st) {
   int rc;
-  uint64_t cap;
-  if (blocks > c->dec_cap) {
-    if ((rc = grow(st, &c->dec_agg, &c->dec_cap, blocks, 3))) return rc;
-  }
+  if ((rc = c->dec_agg.grow(st, blocks, 3))) return rc;
   const uint64_t tiles = (blocks + kTile - 1) / kTile;
-  if (tiles > c->tile_cap) {
-    cap = c->tile_cap;
-    if ((rc = grow(st, &c->tile_sum, &cap, tiles, 3))) return rc;
-    cap = c->tile_cap;
-    if ((rc = grow(st, &c->tile_pre, &cap, tiles, 3))) return rc;
-    c->tile_cap = cap;
-  }
+  if ((rc = c->tile_sum.grow(st, tiles, 3)) || (rc = c->tile_pre.grow(st, tiles, 3))) return rc;
+  // fresh status memory is all zero: the next call starts a new epoch sequence
+  bool fresh = false;
   if (blocks > c->lag_blk_cap) {
     // one arena: per block 3 aggregate + 3 base granules, then per tile 3 aggregate + 3 inclusive
     const uint64_t nb = blocks + blocks / 4 + 1024;
-    cap = 0;  // (grow frees the old arena)
-    if ((rc = grow(st, &c->lag_gran, &cap, lag_words(nb), 1, kStatusFlags))) {
-      c->lag_blk_cap = 0;
-      return rc;
-    }
-    c->lag_blk_cap = nb;
-    c->epoch = 0;  // the fresh arena is zeroed; the next call starts a new epoch sequence
+    c->lag_blk_cap = 0;
+    rc = c->lag_gran.grow(st, lag_words(nb), 1, &fresh);
+    // (lag_words(nb) passes what the arena holds, so grow reallocates; were it ever to keep the
+    // arena, the layout below still moves with lag_blk_cap: a new epoch sequence either way)
+    if (!rc) c->lag_blk_cap = nb, fresh = true;
   }
-  if (segs > c->seg_cap) {
-    cap = c->seg_cap;
-    if ((rc = grow(st, &c->seg_agg, &cap, segs, 2, kStatusFlags))) return rc;
-    cap = c->seg_cap;
-    if ((rc = grow(st, &c->seg_inc, &cap, segs, 2, kStatusFlags))) return rc;
-    c->seg_cap = cap;
-    c->epoch = 0;
-  }
-  if (entries + 1 > c->rec_cap) {
-    cap = c->rec_cap;
-    if ((rc = grow(st, &c->rec_first, &cap, entries + 1, 1))) return rc;
-    cap = c->rec_cap;
-    if ((rc = grow(st, &c->blk_first, &cap, entries + 1, 1))) return rc;
-    cap = c->rec_cap;
-    if ((rc = grow(st, &c->ent, &cap, entries + 1, 1))) return rc;
-    cap = c->rec_cap;
-    if ((rc = grow(st, &c->big_list, &cap, entries + 1, 1))) return rc;
-    cap = c->rec_cap;
-    if ((rc = grow(st, &c->blk_sz, &cap, entries + 1, 1))) return rc;
-    c->rec_cap = cap;
-  }
+  if (!rc) rc = c->seg_agg.grow(st, segs, 2, &fresh);
+  if (!rc) rc = c->seg_inc.grow(st, segs, 2, &fresh);
+  if (fresh) c->epoch = 0;
+  if (rc) return rc;
+  for (DevBuf<uint32_t>* b : {&c->rec_first, &c->blk_first, &c->ent, &c->big_list, &c->blk_sz})
+    if ((rc = b->grow(st, entries + 1, 1))) return rc;
   return LSMBLK_OK;
 }
 
 // Next look-back epoch; on wrap the status arrays are cleared on the stream.
 int next_epoch(lsmblk_ctx* c, hipStream_t st) {
   if (c->epoch == 0 || c->epoch >= 16383) {
-    if (c->seg_cap) {
-      if (hipMemsetAsync(c->seg_agg, 0, c->seg_cap * 2 * 8, st) != hipSuccess) return LSMBLK_E_HIP;
-      if (hipMemsetAsync(c->seg_inc, 0, c->seg_cap * 2 * 8, st) != hipSuccess) return LSMBLK_E_HIP;
-    }
-    if (c->lag_blk_cap) {
-      if (hipMemsetAsync(c->lag_gran, 0, lag_words(c->lag_blk_cap) * 8, st) != hipSuccess) return LSMBLK_E_HIP;
-    }
-    if (c->frec_cap && hipMemsetAsync(c->frec, 0, c->frec_cap * 4 * 8, st) != hipSuccess) return LSMBLK_E_HIP;
-    if (c->fdone_cap && hipMemsetAsync(c->fdone, 0, c->fdone_cap * 8, st) != hipSuccess) return LSMBLK_E_HIP;
+    for (const DevBufBase* b = c->bufs; b; b = b->next)  // every status array the context has
+      if (b->status && !b->zero(st)) return LSMBLK_E_HIP;
     c->epoch = 0;
   }
   ++c->epoch;
@@ -4166,6 +4135,43 @@ int next_epoch(lsmblk_ctx* c, hipStream_t st) {
 }
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// The context's stats words of a CRC pass whose errors another kernel reports (first use).
+int ensure_cstats(lsmblk_ctx* c) {
+  if (c->meta_cstats || hipMalloc(reinterpret_cast<void**>(&c->meta_cstats), LSMBLK_STATS_WORDS * 8) == hipSuccess)
+    return LSMBLK_OK;
+  c->meta_cstats = nullptr;
+  return LSMBLK_E_NOMEM;
+}
+
+// What the two filter calls share: the workspace for in->n entries and the FiltArgs fields that
+// name the streams, the workspace and the stats (the rules' fields zero).
+int filt_prepare(lsmblk_ctx* c, const lsmblk_kv_stream* in, const lsmblk_kv_stream* out, uint64_t* stats,
+                 hipStream_t st, FiltArgs& a) {
+  const uint64_t ntiles = (in->n + kFiltTile - 1) / kFiltTile;
+  int rc;
+  if ((rc = c->filt_keep.grow(st, in->n + 1, 1)) || (rc = c->filt_tile.grow(st, ntiles + 1, 6))) return rc;
+  memset(&a, 0, sizeof(a));
+  a.keys = in->keys;
+  a.key_off = in->key_off;
+  a.vals = in->vals;
+  a.val_off = in->val_off;
+  a.ts = in->ts;
+  a.n = in->n;
+  a.okeys = out->keys;
+  a.okey_off = out->key_off;
+  a.ovals = out->vals;
+  a.oval_off = out->val_off;
+  a.ots = out->ts;
+  a.entry_cap = out->entry_cap;
+  a.key_cap = out->key_cap;
+  a.val_cap = out->val_cap;
+  a.keep = c->filt_keep;
+  a.tile_sum = c->filt_tile;
+  a.tile_pre = c->filt_tile + 3 * c->filt_tile.cap;
+  a.stats = stats;
+  return LSMBLK_OK;
+}
 
 }  // namespace lsmblk_impl
 
@@ -4201,33 +4207,9 @@ void lsmblk_ctx_destroy(lsmblk_ctx* c) {
   if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
   if (c->join_ev) (void)hipEventDestroy(c->join_ev);
   (void)hipFree(c->counters);
-  release(c->dec_agg);
-  release(c->tile_sum);
-  release(c->tile_pre);
-  release(c->seg_agg, kStatusFlags);
-  release(c->seg_inc, kStatusFlags);
-  release(c->rec_first);
-  release(c->ent);
-  release(c->big_list);
-  release(c->blk_sz);
-  release(c->frec, kStatusFlags);
-  release(c->fdone, kStatusFlags);
-  release(c->fwnb);
-  release(c->fbig);
-  release(c->blk_first);
   (void)hipFree(c->crc_tabs);
-  release(c->meta_rec);
-  release(c->meta_pos);
-  release(c->meta_tile);
-  release(c->meta_crc);
   (void)hipFree(c->meta_cstats);
-  release(c->filt_keep);
-  release(c->filt_tile);
-  release(c->cws);
-  release(c->vcrc);
-  release(c->sws);
-  release(c->rws);
-  release(c->lag_gran, kStatusFlags);
+  for (DevBufBase* b = c->bufs; b; b = b->next) b->release();
   (void)hipStreamSynchronize(nullptr);  // (the pool frees above were queued on the null stream)
   (void)hipFree(c->dbg);
   for (auto& e : c->klog) {
@@ -4350,9 +4332,8 @@ int lsmblk_ctx_kernel_log(lsmblk_ctx* c, lsmblk_kernel_stat* out, uint32_t cap, 
 
 int lsmblk_ctx_reserve(lsmblk_ctx* c, uint64_t max_blocks, uint64_t max_entries, uint64_t max_segments) {
   if (!c) return LSMBLK_E_INVAL;
-  std::lock_guard<std::mutex> g(c->mu);
-  DeviceGuard dg(c->device, c);
-  if (!dg.ok) return LSMBLK_E_HIP;
+  CallGuard call(c, nullptr);
+  if (call.rc) return call.rc;
   // (on the null stream, completed before returning: a later call may come on any stream)
   const int rc = reserve_locked(c, max_blocks, max_entries, max_segments, nullptr);
   if (rc) return rc;
@@ -4371,30 +4352,36 @@ int lsmblk_decode_batch_ex(lsmblk_ctx* c, const uint8_t* blocks, const uint64_t*
   if (!aligned16(out->keys) || !aligned16(out->vals) || !out->key_off || !out->val_off) return LSMBLK_E_INVAL;
   if (nblk > 0x7FFFFFFFull || tail > 16) return LSMBLK_E_INVAL;  // one workgroup (or wave) per block
   if ((flags & LSMBLK_DECODE_VERIFY_CRC) && tail != 4) return LSMBLK_E_INVAL;
-  std::lock_guard<std::mutex> g(c->mu);
-  DeviceGuard dg(c->device, c);
-  if (!dg.ok) return LSMBLK_E_HIP;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  CallGuard call(c, stream);
+  if (call.rc) return call.rc;
+  hipStream_t st = call.st;
   int rc = reserve_locked(c, nblk, 0, 0, st);
   if (rc) return rc;
+  // (after the growth, as the call has always queued it: its stream operations keep their order)
   if (hipMemsetAsync(stats, 0, LSMBLK_STATS_WORDS * 8, st) != hipSuccess) return LSMBLK_E_HIP;
   if (nblk == 0) {
     LSM_LAUNCH(finish_empty_decode, dim3(1), dim3(64), 0, st, out->key_off, out->val_off, out->entry_cap);
     if (blk_ent && hipMemsetAsync(blk_ent, 0, 8, st) != hipSuccess) return LSMBLK_E_HIP;
-    return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
-  }
-  if (flags & LSMBLK_DECODE_VERIFY_CRC) {
-    // read_block's checksum test (src/table.rs:226-230) over the framed ranges, then the decode
-    if ((rc = lsmblk_impl::ensure_crc_tabs(c, st))) return rc;
-    if ((rc = grow(st, &c->vcrc, &c->vcrc_cap, nblk + 1, 1))) return rc;
-    if (!c->meta_cstats && hipMalloc(reinterpret_cast<void**>(&c->meta_cstats), LSMBLK_STATS_WORDS * 8) != hipSuccess) {
-      c->meta_cstats = nullptr;
-      return LSMBLK_E_NOMEM;
-    }
-    if (hipMemsetAsync(c->meta_cstats, 0, LSMBLK_STATS_WORDS * 8, st) != hipSuccess) return LSMBLK_E_HIP;
+    return launch_rc();
   }
   const uint64_t ntiles = (nblk + kTile - 1) / kTile;
   const KLogRange lr(c, &c->dec_log0, &c->dec_log1);
+  if (flags & LSMBLK_DECODE_VERIFY_CRC) {
+    // read_block's checksum test (src/table.rs:226-230) over the framed ranges, then the decode, on
+    // the same stream (round 4: the two-pass decode with the count folded into the old CRC pass,
+    // 4.0 ms at U; the lagged decode beside that CRC pass on a second stream, 5.07 ms -- the
+    // persistent CRC grid and the lagged decode's dispatch-order schedule got in each other's way).
+    // Two-pass (A/B): the same pass takes every block's (entries, key bytes, value bytes) as well,
+    // in place of the count pass's second read of E.
+    if ((rc = lsmblk_impl::ensure_crc_tabs(c, st)) || (rc = c->vcrc.grow(st, nblk + 1, 1)) || (rc = ensure_cstats(c)))
+      return rc;
+    if (hipMemsetAsync(c->meta_cstats, 0, LSMBLK_STATS_WORDS * 8, st) != hipSuccess) return LSMBLK_E_HIP;
+    if ((rc = lsmblk_impl::launch_crc(c, blocks, blk_off, nblk, tail, c->vcrc, c->meta_cstats, st,
+                                      c->dec_two_pass ? c->dec_agg.get() : nullptr)))
+      return rc;
+    LSM_LAUNCH(crc_verify_kernel, dim3(uint32_t((nblk + 255) / 256)), dim3(256), 0, st, blocks, blk_off, nblk,
+               c->vcrc.get(), c->meta_cstats, stats);
+  }
   DecodeArgs a;
   a.blocks = blocks;
   a.blk_off = blk_off;
@@ -4417,17 +4404,7 @@ int lsmblk_decode_batch_ex(lsmblk_ctx* c, const uint8_t* blocks, const uint64_t*
   a.lag = a.lag_bytes = 0;
   a.tag = a.poll = 0;
   if (!c->dec_two_pass) {
-    // lagged decode: E is read from HBM once, one launch (decode_lag_kernel).  The CRC-verifying
-    // read runs the streaming CRC pass and the checksum test first, on the same stream (round 4:
-    // the two-pass decode with the count folded into the old CRC pass, 4.0 ms at U; the lagged
-    // decode beside that CRC pass on a second stream, 5.07 ms -- the persistent CRC grid and the
-    // lagged decode's dispatch-order schedule got in each other's way).
-    if (flags & LSMBLK_DECODE_VERIFY_CRC) {
-      if ((rc = lsmblk_impl::launch_crc(c, blocks, blk_off, nblk, tail, c->vcrc, c->meta_cstats, st)))
-        return rc;
-      LSM_LAUNCH(crc_verify_kernel, dim3(uint32_t((nblk + 255) / 256)), dim3(256), 0, st, blocks, blk_off, nblk,
-                 c->vcrc, c->meta_cstats, stats);
-    }
+    // lagged decode: E is read from HBM once, one launch (decode_lag_kernel)
     if ((rc = next_epoch(c, st))) return rc;
     a.bagg = c->lag_gran;
     a.bbase = a.bagg + 3 * c->lag_blk_cap;
@@ -4443,18 +4420,9 @@ int lsmblk_decode_batch_ex(lsmblk_ctx* c, const uint8_t* blocks, const uint64_t*
     a.tag = c->epoch;
     a.poll = c->poll;
     LSM_LAUNCH_SLOT(2, decode_lag_kernel, dim3(uint32_t(nblk + a.lag)), dim3(64), 0, st, a);
-    return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
+    return launch_rc();
   }
-  if (flags & LSMBLK_DECODE_VERIFY_CRC) {
-    // (two-pass A/B) one pass over E: the CRC of every block and its (entries, key bytes, value
-    // bytes), in place of the count pass's second read of E
-    if ((rc = lsmblk_impl::launch_crc(c, blocks, blk_off, nblk, tail, c->vcrc, c->meta_cstats, st, c->dec_agg)))
-      return rc;
-    LSM_LAUNCH(crc_verify_kernel, dim3(uint32_t((nblk + 255) / 256)), dim3(256), 0, st, blocks, blk_off, nblk,
-                       c->vcrc, c->meta_cstats, stats);
-    LSM_LAUNCH_SLOT(0, agg_tile_kernel, dim3(uint32_t((ntiles + 3) / 4)), dim3(256), 0, st, (const uint32_t*)c->dec_agg, nblk,
-            c->tile_sum);
-  } else {
+  if (!(flags & LSMBLK_DECODE_VERIFY_CRC)) {  // (else the CRC pass has counted)
     CountArgs ca;
     ca.blocks = blocks;
     ca.blk_off = blk_off;
@@ -4464,9 +4432,9 @@ int lsmblk_decode_batch_ex(lsmblk_ctx* c, const uint8_t* blocks, const uint64_t*
     ca.stats = stats;
     ca.tail = tail;
     LSM_LAUNCH_SLOT(0, dec_count_staged_kernel, dim3(uint32_t(nblk)), dim3(64), 0, st, ca);
-    LSM_LAUNCH_SLOT(0, agg_tile_kernel, dim3(uint32_t((ntiles + 3) / 4)), dim3(256), 0, st, (const uint32_t*)c->dec_agg,
-            nblk, c->tile_sum);
   }
+  LSM_LAUNCH_SLOT(0, agg_tile_kernel, dim3(uint32_t((ntiles + 3) / 4)), dim3(256), 0, st, (const uint32_t*)c->dec_agg,
+                  nblk, c->tile_sum.get());
   ScanArgs sa;
   sa.tile_sum = c->tile_sum;
   sa.tile_pre = c->tile_pre;
@@ -4481,7 +4449,7 @@ int lsmblk_decode_batch_ex(lsmblk_ctx* c, const uint8_t* blocks, const uint64_t*
   sa.nblk = nblk;
   LSM_LAUNCH_SLOT(1, dec_scan_kernel, dim3(1), dim3(1024), 0, st, sa);
   LSM_LAUNCH_SLOT(2, decode_kernel, dim3(uint32_t(nblk)), dim3(64), 0, st, a);
-  return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
+  return launch_rc();
 }
 
 int lsmblk_encode_batch(lsmblk_ctx* c, const lsmblk_kv_stream* in, const uint32_t* seg_start, uint32_t nseg,
@@ -4498,51 +4466,60 @@ int lsmblk_encode_batch_ex(lsmblk_ctx* c, const lsmblk_kv_stream* in, const uint
   if (in->n >= 0xFFFFFFFFull || !in->key_off || !in->val_off) return LSMBLK_E_INVAL;
   if (block_size == 0 || (flags & ~uint32_t(LSMBLK_ENCODE_SEG_SLOTS | LSMBLK_ENCODE_FRAMED))) return LSMBLK_E_INVAL;
   if ((flags & LSMBLK_ENCODE_SEG_SLOTS) && !seg_out) return LSMBLK_E_INVAL;
-  std::lock_guard<std::mutex> g(c->mu);
-  DeviceGuard dg(c->device, c);
-  if (!dg.ok) return LSMBLK_E_HIP;
-  return lsmblk_impl::encode_locked(c, in, nullptr, seg_start, nullptr, nseg, block_size, out, out_cap, blk_off,
-                                    blk_cap, stats, reinterpret_cast<hipStream_t>(stream), false, flags, seg_out);
+  CallGuard call(c, stream);
+  if (call.rc) return call.rc;
+  lsmblk_impl::EncodeReq q;
+  q.st = call.st;
+  q.in = in;
+  q.seg_start = seg_start;
+  q.nseg = nseg;
+  q.block_size = block_size;
+  q.out = out;
+  q.out_cap = out_cap;
+  q.blk_off = blk_off;
+  q.blk_cap = blk_cap;
+  q.stats = stats;
+  q.flags = flags;
+  q.seg_out = seg_out;
+  return lsmblk_impl::encode_locked(c, q);
 }
 
 }  // extern "C"
 
 namespace lsmblk_impl {
-int encode_locked(lsmblk_ctx* c, const lsmblk_kv_stream* in, const uint64_t* dn, const uint32_t* seg_start,
-                  const uint32_t* dnseg, uint32_t nseg, uint32_t block_size, uint8_t* out, uint64_t out_cap,
-                  uint64_t* blk_off, uint64_t blk_cap, uint64_t* stats, hipStream_t st, bool span, uint32_t flags,
-                  uint64_t* seg_out) {
+int encode_locked(lsmblk_ctx* c, const EncodeReq& q) {
+  hipStream_t st = q.st;
+  const lsmblk_kv_stream* const in = q.in;
   const KLogRange lr(c, &c->enc_log0, &c->enc_log1);
-  const bool slots = (flags & LSMBLK_ENCODE_SEG_SLOTS) != 0;
-  const bool framed = (flags & LSMBLK_ENCODE_FRAMED) != 0;
-  if (slots && (!seg_out || span || dn || dnseg)) return LSMBLK_E_INVAL;
-  if (framed && (span || dn || dnseg)) return LSMBLK_E_INVAL;
+  const bool slots = (q.flags & LSMBLK_ENCODE_SEG_SLOTS) != 0;
+  const bool framed = (q.flags & LSMBLK_ENCODE_FRAMED) != 0;
+  if (slots && (!q.seg_out || q.span || q.dn || q.dnseg)) return LSMBLK_E_INVAL;
+  if (framed && (q.span || q.dn || q.dnseg)) return LSMBLK_E_INVAL;
   // in->n (and nseg) are upper bounds when dn (dnseg) point at the device-side values
-  int rc = reserve_locked(c, 0, in->n, nseg, st);
+  int rc = reserve_locked(c, 0, in->n, q.nseg, st);
   if (rc) return rc;
-  if (hipMemsetAsync(stats, 0, LSMBLK_STATS_WORDS * 8, st) != hipSuccess) return LSMBLK_E_HIP;
-  if (nseg == 0) {
+  if (hipMemsetAsync(q.stats, 0, LSMBLK_STATS_WORDS * 8, st) != hipSuccess) return LSMBLK_E_HIP;
+  if (q.nseg == 0) {
     // no segments: zero blocks; blk_off[0] = 0
     if (in->n != 0) return LSMBLK_E_INVAL;
-    if (blk_cap >= 1 && hipMemsetAsync(blk_off, 0, 8, st) != hipSuccess) return LSMBLK_E_HIP;
+    if (q.blk_cap >= 1 && hipMemsetAsync(q.blk_off, 0, 8, st) != hipSuccess) return LSMBLK_E_HIP;
     return LSMBLK_OK;
   }
   const int cus = cu_count(c);
   // the fused walk + emit (A/B only: the walk's instructions compete with emit's for the same
   // issue slots): per-segment slots, blocks no larger than emit's LDS image
-  const bool fused = slots && !framed && block_size <= 4096 && c->fuse_on;
+  const bool fused = slots && !framed && q.block_size <= 4096 && c->fuse_on;
   uint32_t walk_wgs = 0, nwalk = 0;
   if (fused) {
-    walk_wgs = uint32_t(std::min<uint64_t>(uint64_t(cus), (uint64_t(nseg) + 1) / 2));
+    walk_wgs = uint32_t(std::min<uint64_t>(uint64_t(cus), (uint64_t(q.nseg) + 1) / 2));
     walk_wgs += walk_wgs & 1;  // walkers a multiple of 4: emitters split evenly over them
     nwalk = 2 * walk_wgs;
     const uint64_t recs = in->n + nwalk + 1;
-    const uint64_t fc = c->frec_cap, dc = c->fdone_cap;
-    if ((rc = grow(st, &c->frec, &c->frec_cap, recs, 4, kStatusFlags))) return rc;
-    if ((rc = grow(st, &c->fdone, &c->fdone_cap, nwalk, 1, kStatusFlags))) return rc;
-    if ((rc = grow(st, &c->fwnb, &c->fwnb_cap, nwalk, 1))) return rc;
-    if ((rc = grow(st, &c->fbig, &c->fbig_cap, recs, 1))) return rc;
-    if (c->frec_cap != fc || c->fdone_cap != dc) c->epoch = 0;  // fresh granules: a new epoch sequence
+    bool fresh = false;
+    rc = c->frec.grow(st, recs, 4, &fresh);
+    if (!rc) rc = c->fdone.grow(st, nwalk, 1, &fresh);
+    if (fresh) c->epoch = 0;  // fresh granules: a new epoch sequence
+    if (rc || (rc = c->fwnb.grow(st, nwalk, 1)) || (rc = c->fbig.grow(st, recs, 1))) return rc;
   }
   if (framed && (rc = ensure_crc_tabs(c, st))) return rc;
   if ((rc = next_epoch(c, st))) return rc;
@@ -4552,27 +4529,27 @@ int encode_locked(lsmblk_ctx* c, const lsmblk_kv_stream* in, const uint64_t* dn,
   p.key_off = in->key_off;
   p.val_off = in->val_off;
   p.n = in->n;
-  p.seg_start = seg_start;
-  p.nseg = nseg;
-  p.block_size = block_size;
+  p.seg_start = q.seg_start;
+  p.nseg = q.nseg;
+  p.block_size = q.block_size;
   p.sz = c->ent;
   p.rec_first = c->rec_first;
   p.blk_first = c->blk_first;
-  p.blk_off = blk_off;
-  p.blk_cap = blk_cap;
-  p.out_cap = out_cap;
-  p.stats = stats;
+  p.blk_off = q.blk_off;
+  p.blk_cap = q.blk_cap;
+  p.out_cap = q.out_cap;
+  p.stats = q.stats;
   p.ticket = c->counters + 256;
   p.agg = c->seg_agg;
   p.inc = c->seg_inc;
   p.tag = c->epoch;
   p.poll = c->poll;
-  p.dn = dn;
-  p.dnseg = dnseg;
-  p.span = span ? 1u : 0u;
+  p.dn = q.dn;
+  p.dnseg = q.dnseg;
+  p.span = q.span ? 1u : 0u;
   p.skip = c->skip;
   p.dbg = c->dbg_on ? c->dbg : nullptr;
-  p.seg_out = slots ? seg_out : nullptr;
+  p.seg_out = slots ? q.seg_out : nullptr;
   p.blk_sz = slots || framed ? c->blk_sz : nullptr;
   p.pipe_helper = c->plan_pipe ? 1u : 0u;
   p.frame = framed ? 4u : 0u;
@@ -4583,16 +4560,16 @@ int encode_locked(lsmblk_ctx* c, const lsmblk_kv_stream* in, const uint64_t* dn,
   e.val_off = in->val_off;
   e.ts = in->ts;
   e.blk_first = c->blk_first;
-  e.blk_off = blk_off;
-  e.out = out;
-  e.out_cap = out_cap;
-  e.blk_cap = blk_cap;
+  e.blk_off = q.blk_off;
+  e.out = q.out;
+  e.out_cap = q.out_cap;
+  e.blk_cap = q.blk_cap;
   e.n = in->n;
-  e.stats = stats;
-  e.big_flag = reinterpret_cast<uint8_t*>(c->big_list);
+  e.stats = q.stats;
+  e.big_flag = reinterpret_cast<uint8_t*>(c->big_list.get());
   e.blk_sz = slots || framed ? c->blk_sz : nullptr;
   e.skip = c->skip;
-  e.dn = dn;
+  e.dn = q.dn;
   if (fused) {
     if (p.dbg && hipMemsetAsync(p.dbg, 0, kDbgWords * 8, st) != hipSuccess) return LSMBLK_E_HIP;
     FuseArgs f;
@@ -4601,30 +4578,30 @@ int encode_locked(lsmblk_ctx* c, const lsmblk_kv_stream* in, const uint64_t* dn,
     f.rec = c->frec;
     f.wdone = c->fdone;
     f.wnb = c->fwnb;
-    f.seg_out = seg_out;
+    f.seg_out = q.seg_out;
     f.bigr = c->fbig;
     f.nwalk = nwalk;
-    f.spw = uint32_t((uint64_t(nseg) + nwalk - 1) / nwalk);
+    f.spw = uint32_t((uint64_t(q.nseg) + nwalk - 1) / nwalk);
     f.walk_wgs = walk_wgs;
     // three emit workgroups per CU beside the walkers' one, split evenly over the walkers
     f.per_walker = std::max<uint32_t>(1u, uint32_t(3ull * kEmitWaves * uint64_t(cus) / nwalk));
     const uint32_t emit_wgs = f.per_walker * nwalk / kEmitWaves;
     LSM_LAUNCH_SLOT(4, encode_fused_kernel, dim3(walk_wgs + emit_wgs), dim3(256), 0, st, f);
-    LSM_LAUNCH(slot_tables_kernel, dim3(nwalk), dim3(256), 0, st, f, c->blk_first, c->blk_sz,
-               reinterpret_cast<uint8_t*>(c->big_list), blk_off, blk_cap, out_cap);
+    LSM_LAUNCH(slot_tables_kernel, dim3(nwalk), dim3(256), 0, st, f, c->blk_first.get(), c->blk_sz.get(),
+               reinterpret_cast<uint8_t*>(c->big_list.get()), q.blk_off, q.blk_cap, q.out_cap);
   } else {
     if (p.dbg && hipMemsetAsync(p.dbg, 0, kDbgWords * 8, st) != hipSuccess) return LSMBLK_E_HIP;
-    LSM_LAUNCH_SLOT(3, plan_walk_kernel, dim3((nseg + 3) / 4), dim3(kWalkThreads), 0, st, p);
+    LSM_LAUNCH_SLOT(3, plan_walk_kernel, dim3((q.nseg + 3) / 4), dim3(kWalkThreads), 0, st, p);
     if (c->skip & (3u << 16)) {  // plan ablation: the block tables are wrong, emit is not launched
-      return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
+      return launch_rc();
     }
     if (kDiag && c->emit_poison)  // fault injection (diagnostics builds): a corrupt block table
-      LSM_LAUNCH(emit_poison_kernel, dim3(uint32_t(in->n / (5 * 256) + 1)), dim3(256), 0, st, c->blk_first, stats);
+      LSM_LAUNCH(emit_poison_kernel, dim3(uint32_t(in->n / (5 * 256) + 1)), dim3(256), 0, st, c->blk_first.get(), q.stats);
     // the big-block flags are cleared before emit (the start of emit_kernel to the end of
     // emit_big_kernel is what bench.py's roofline divides by)
-    const uint64_t nblk_max = blk_cap < in->n + 1 ? blk_cap : in->n + 1;  // blocks <= entries, <= blk_cap
+    const uint64_t nblk_max = q.blk_cap < in->n + 1 ? q.blk_cap : in->n + 1;  // blocks <= entries, <= blk_cap
     if (nblk_max && hipMemsetAsync(c->big_list, 0, nblk_max, st) != hipSuccess) return LSMBLK_E_HIP;
-    if (hipGetLastError() != hipSuccess) return LSMBLK_E_HIP;
+    if (launch_rc()) return LSMBLK_E_HIP;
     if ((c->emit_mode ? c->emit_mode : kEmitModeDefault) == 2) {
       // one single-wave workgroup per block the call can produce; beyond the clamp (a loose
       // blk_cap: workgroups past the plan's block count only read stats and leave) workgroup j
@@ -4633,30 +4610,23 @@ int encode_locked(lsmblk_ctx* c, const lsmblk_kv_stream* in, const uint64_t* dn,
       const uint32_t grid = uint32_t(std::max<uint64_t>(1, std::min(nblk_max, clamp)));
       LSM_LAUNCH_SLOT(4, emit_block_kernel, dim3(grid), dim3(64), 0, st, e);
     } else {
-      int per_cu = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, emit_kernel, 256, 0) != hipSuccess || per_cu < 1)
-        per_cu = 3;
-      const uint32_t grid = uint32_t(cus) * uint32_t(per_cu);
-      LSM_LAUNCH_SLOT(4, emit_kernel, dim3(grid), dim3(256), 0, st, e);
+      LSM_LAUNCH_SLOT(4, emit_kernel, dim3(resident_wgs(cus, emit_kernel, 256, 3)), dim3(256), 0, st, e);
     }
   }
   // (every workgroup resident at once: the flagged blocks are strided over the whole grid)
-  int big_cu = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&big_cu, emit_big_kernel, 256, 0) != hipSuccess || big_cu < 1)
-    big_cu = 4;
-  LSM_LAUNCH_SLOT(4, emit_big_kernel, dim3(uint32_t(cus) * uint32_t(big_cu)), dim3(256), 0, st, e);
+  LSM_LAUNCH_SLOT(4, emit_big_kernel, dim3(resident_wgs(cus, emit_big_kernel, 256, 4)), dim3(256), 0, st, e);
   if (framed) {  // every block's CRC after it: the SST data section (src/table/builder.rs:112-123)
-    const uint64_t nblk_max = blk_cap < in->n + 1 ? blk_cap : in->n + 1;
-    if ((rc = launch_crc_frames(c, out, blk_off, c->blk_sz, nblk_max, stats, st))) return rc;
+    const uint64_t nblk_max = q.blk_cap < in->n + 1 ? q.blk_cap : in->n + 1;
+    if ((rc = launch_crc_frames(c, q.out, q.blk_off, c->blk_sz, nblk_max, q.stats, st))) return rc;
   }
-  return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
+  return launch_rc();
 }
 
 int segment_blocks_locked(lsmblk_ctx* c, const uint32_t* seg_start, uint32_t nseg_max, const uint64_t* enc_stats,
                           uint32_t* seg_blk, hipStream_t st) {
   LSM_LAUNCH(seg_blocks_kernel, dim3(uint32_t((uint64_t(nseg_max) + 256) / 256)), dim3(256), 0, st,
-                     c->blk_first, enc_stats, seg_start, nseg_max, seg_blk);
-  return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
+                     c->blk_first.get(), enc_stats, seg_start, nseg_max, seg_blk);
+  return launch_rc();
 }
 }  // namespace lsmblk_impl
 
@@ -4665,28 +4635,20 @@ extern "C" {
 int lsmblk_crc32_batch(lsmblk_ctx* c, const uint8_t* blocks, const uint64_t* blk_off, uint64_t nblk, uint32_t tail,
                        uint32_t* crc, uint64_t* stats, void* stream) {
   if (!c || !blk_off || !stats || (nblk && !crc)) return LSMBLK_E_INVAL;
-  std::lock_guard<std::mutex> g(c->mu);
-  DeviceGuard dg(c->device, c);
-  if (!dg.ok) return LSMBLK_E_HIP;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  int rc = lsmblk_impl::ensure_crc_tabs(c, st);
-  if (rc) return rc;
-  if (hipMemsetAsync(stats, 0, LSMBLK_STATS_WORDS * 8, st) != hipSuccess) return LSMBLK_E_HIP;
-  if (nblk == 0) return LSMBLK_OK;
-  return lsmblk_impl::launch_crc(c, blocks, blk_off, nblk, tail, crc, stats, st);
+  CallGuard call(c, stream, stats, LSMBLK_STATS_WORDS);
+  if (call.rc) return call.rc;
+  const int rc = lsmblk_impl::ensure_crc_tabs(c, call.st);
+  if (rc || nblk == 0) return rc;
+  return lsmblk_impl::launch_crc(c, blocks, blk_off, nblk, tail, crc, stats, call.st);
 }
 
 int lsmblk_encode_segment_blocks(lsmblk_ctx* c, const uint32_t* seg_start, uint32_t nseg, const uint64_t* enc_stats,
                                  uint32_t* seg_blk, void* stream) {
   if (!c || !seg_start || !enc_stats || !seg_blk) return LSMBLK_E_INVAL;
-  std::lock_guard<std::mutex> g(c->mu);
-  DeviceGuard dg(c->device, c);
-  if (!dg.ok) return LSMBLK_E_HIP;
+  CallGuard call(c, stream);
+  if (call.rc) return call.rc;
   if (!c->blk_first) return LSMBLK_E_INVAL;  // no encode ran on this context
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  LSM_LAUNCH(seg_blocks_kernel, dim3(uint32_t((uint64_t(nseg) + 256) / 256)), dim3(256), 0, st,
-                     c->blk_first, enc_stats, seg_start, nseg, seg_blk);
-  return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
+  return lsmblk_impl::segment_blocks_locked(c, seg_start, nseg, enc_stats, seg_blk, call.st);
 }
 
 int lsmblk_block_meta_batch(lsmblk_ctx* c, const uint8_t* blocks, const uint64_t* blk_off, uint64_t nblk,
@@ -4694,11 +4656,10 @@ int lsmblk_block_meta_batch(lsmblk_ctx* c, const uint8_t* blocks, const uint64_t
                             uint64_t* meta_off, uint64_t* stats, void* stream) {
   if (!c || !blk_off || !seg_blk || !meta_off || !stats || !meta || meta_cap < 16) return LSMBLK_E_INVAL;
   if (nseg == 0 || nblk >= 0xFFFFFFFFull) return LSMBLK_E_INVAL;
-  std::lock_guard<std::mutex> g(c->mu);
-  DeviceGuard dg(c->device, c);
-  if (!dg.ok) return LSMBLK_E_HIP;
+  CallGuard call(c, stream);
+  if (call.rc) return call.rc;
   return lsmblk_impl::block_meta_locked(c, blocks, blk_off, nblk, tail, seg_blk, nseg, meta, meta_cap, meta_off,
-                                        stats, reinterpret_cast<hipStream_t>(stream));
+                                        stats, call.st);
 }
 
 }  // extern "C"
@@ -4710,19 +4671,9 @@ int block_meta_locked(lsmblk_ctx* c, const uint8_t* blocks, const uint64_t* blk_
   int rc = lsmblk_impl::ensure_crc_tabs(c, st);
   if (rc) return rc;
   const uint64_t ntiles = (nblk + kMetaTile - 1) / kMetaTile;
-  if (nblk + 1 > c->meta_blk_cap) {
-    uint64_t cap = c->meta_blk_cap;
-    if ((rc = grow(st, &c->meta_rec, &cap, nblk + 1, 1))) return rc;
-    cap = c->meta_blk_cap;
-    if ((rc = grow(st, &c->meta_pos, &cap, nblk + 1, 1))) return rc;
-    c->meta_blk_cap = cap;
-  }
-  if ((rc = grow(st, &c->meta_tile, &c->meta_tile_cap, ntiles + 1, 2))) return rc;
-  if ((rc = grow(st, &c->meta_crc, &c->meta_seg_cap, nseg, 1))) return rc;
-  if (!c->meta_cstats && hipMalloc(reinterpret_cast<void**>(&c->meta_cstats), LSMBLK_STATS_WORDS * 8) != hipSuccess) {
-    c->meta_cstats = nullptr;
-    return LSMBLK_E_NOMEM;
-  }
+  if ((rc = c->meta_rec.grow(st, nblk + 1, 1)) || (rc = c->meta_pos.grow(st, nblk + 1, 1))) return rc;
+  if ((rc = c->meta_tile.grow(st, ntiles + 1, 2)) || (rc = c->meta_crc.grow(st, nseg, 1))) return rc;
+  if ((rc = ensure_cstats(c))) return rc;
   if (hipMemsetAsync(stats, 0, LSMBLK_STATS_WORDS * 8, st) != hipSuccess) return LSMBLK_E_HIP;
   MetaArgs a;
   a.blocks = blocks;
@@ -4736,7 +4687,7 @@ int block_meta_locked(lsmblk_ctx* c, const uint8_t* blocks, const uint64_t* blk_
   a.meta_off = meta_off;
   a.rec = c->meta_rec;
   a.tile_sum = c->meta_tile;
-  a.tile_pre = c->meta_tile + c->meta_tile_cap;
+  a.tile_pre = c->meta_tile + c->meta_tile.cap;
   a.pos = c->meta_pos;
   a.crc = c->meta_crc;
   a.crc_stats = c->meta_cstats;
@@ -4746,13 +4697,13 @@ int block_meta_locked(lsmblk_ctx* c, const uint8_t* blocks, const uint64_t* blk_
   LSM_LAUNCH(meta_scan_kernel, dim3(1), dim3(1024), 0, st, a);
   if (ntiles) LSM_LAUNCH(meta_write_kernel, dim3(uint32_t(ntiles)), dim3(256), 0, st, a);
   LSM_LAUNCH(meta_seg_kernel, dim3(sg), dim3(256), 0, st, a);
-  if (hipGetLastError() != hipSuccess) return LSMBLK_E_HIP;
+  if (launch_rc()) return LSMBLK_E_HIP;
   // section CRC over [meta_off[s] + 4, meta_off[s+1] - 4): blocks = meta + 4, tail = 8
   if (hipMemsetAsync(c->meta_cstats, 0, LSMBLK_STATS_WORDS * 8, st) != hipSuccess) return LSMBLK_E_HIP;
   if ((rc = lsmblk_impl::launch_crc(c, meta + 4, meta_off, nseg, 8, c->meta_crc, c->meta_cstats, st, nullptr, true)))
     return rc;
   LSM_LAUNCH(meta_crc_put_kernel, dim3(sg), dim3(256), 0, st, a);
-  return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
+  return launch_rc();
 }
 }  // namespace lsmblk_impl
 
@@ -4764,43 +4715,22 @@ int lsmblk_compact_filter_batch(lsmblk_ctx* c, const lsmblk_kv_stream* in, uint6
   if (!c || !in || !out || !stats || !in->key_off || !in->val_off || !out->key_off || !out->val_off) return LSMBLK_E_INVAL;
   if (nprefix && (!prefixes || !prefix_off)) return LSMBLK_E_INVAL;
   if (in->n >= 0xFFFFFFFFull) return LSMBLK_E_INVAL;
-  std::lock_guard<std::mutex> g(c->mu);
-  DeviceGuard dg(c->device, c);
-  if (!dg.ok) return LSMBLK_E_HIP;
-  const uint64_t n = in->n, ntiles = (n + kFiltTile - 1) / kFiltTile;
-  int rc;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if ((rc = grow(st, &c->filt_keep, &c->filt_cap, n + 1, 1))) return rc;
-  if ((rc = grow(st, &c->filt_tile, &c->filt_tile_cap, ntiles + 1, 6))) return rc;
-  if (hipMemsetAsync(stats, 0, LSMBLK_STATS_WORDS * 8, st) != hipSuccess) return LSMBLK_E_HIP;
+  CallGuard call(c, stream, stats, LSMBLK_STATS_WORDS);
+  if (call.rc) return call.rc;
+  hipStream_t st = call.st;
+  const uint64_t ntiles = (in->n + kFiltTile - 1) / kFiltTile;
   FiltArgs a;
-  a.keys = in->keys;
-  a.key_off = in->key_off;
-  a.vals = in->vals;
-  a.val_off = in->val_off;
-  a.ts = in->ts;
-  a.n = n;
+  const int rc = filt_prepare(c, in, out, stats, st, a);
+  if (rc) return rc;
   a.wm = watermark;
   a.bottom = bottom_level ? 1u : 0u;
   a.npfx = nprefix;
   a.pfx = prefixes;
   a.pfx_off = prefix_off;
-  a.okeys = out->keys;
-  a.okey_off = out->key_off;
-  a.ovals = out->vals;
-  a.oval_off = out->val_off;
-  a.ots = out->ts;
-  a.entry_cap = out->entry_cap;
-  a.key_cap = out->key_cap;
-  a.val_cap = out->val_cap;
-  a.keep = c->filt_keep;
-  a.tile_sum = c->filt_tile;
-  a.tile_pre = c->filt_tile + 3 * c->filt_tile_cap;
-  a.stats = stats;
   if (ntiles) LSM_LAUNCH(filt_flag_kernel, dim3(uint32_t(ntiles)), dim3(256), 0, st, a);
   LSM_LAUNCH(filt_scan_kernel, dim3(1), dim3(1024), 0, st, a);
   if (ntiles) LSM_LAUNCH(filt_write_kernel, dim3(uint32_t(ntiles)), dim3(256), 0, st, a);
-  return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
+  return launch_rc();
 }
 
 int lsmblk_read_filter_batch(lsmblk_ctx* c, const lsmblk_kv_stream* in, const uint32_t* seg_start, const uint64_t* seg_ts,
@@ -4809,35 +4739,13 @@ int lsmblk_read_filter_batch(lsmblk_ctx* c, const lsmblk_kv_stream* in, const ui
   if (!c || !in || !out || !stats || !seg_start || !out_seg_start || !out->key_off || !out->val_off) return LSMBLK_E_INVAL;
   if ((nseg && !seg_ts) || (in->n && (!in->key_off || !in->val_off || !in->ts)) || nseg > 0x7FFFFFFFu) return LSMBLK_E_INVAL;
   if (in->n >= 0xFFFFFFFFull) return LSMBLK_E_INVAL;
-  std::lock_guard<std::mutex> g(c->mu);
-  DeviceGuard dg(c->device, c);
-  if (!dg.ok) return LSMBLK_E_HIP;
-  const uint64_t n = in->n, ntiles = (n + kFiltTile - 1) / kFiltTile;
-  int rc;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if ((rc = grow(st, &c->filt_keep, &c->filt_cap, n + 1, 1))) return rc;
-  if ((rc = grow(st, &c->filt_tile, &c->filt_tile_cap, ntiles + 1, 6))) return rc;
-  if (hipMemsetAsync(stats, 0, LSMBLK_STATS_WORDS * 8, st) != hipSuccess) return LSMBLK_E_HIP;
+  CallGuard call(c, stream, stats, LSMBLK_STATS_WORDS);
+  if (call.rc) return call.rc;
+  hipStream_t st = call.st;
+  const uint64_t ntiles = (in->n + kFiltTile - 1) / kFiltTile;
   ReadFiltArgs a;
-  memset(&a.f, 0, sizeof(a.f));
-  a.f.keys = in->keys;
-  a.f.key_off = in->key_off;
-  a.f.vals = in->vals;
-  a.f.val_off = in->val_off;
-  a.f.ts = in->ts;
-  a.f.n = n;
-  a.f.okeys = out->keys;
-  a.f.okey_off = out->key_off;
-  a.f.ovals = out->vals;
-  a.f.oval_off = out->val_off;
-  a.f.ots = out->ts;
-  a.f.entry_cap = out->entry_cap;
-  a.f.key_cap = out->key_cap;
-  a.f.val_cap = out->val_cap;
-  a.f.keep = c->filt_keep;
-  a.f.tile_sum = c->filt_tile;
-  a.f.tile_pre = c->filt_tile + 3 * c->filt_tile_cap;
-  a.f.stats = stats;
+  const int rc = filt_prepare(c, in, out, stats, st, a.f);
+  if (rc) return rc;
   a.seg_start = seg_start;
   a.seg_ts = seg_ts;
   a.nseg = nseg;
@@ -4846,7 +4754,7 @@ int lsmblk_read_filter_batch(lsmblk_ctx* c, const lsmblk_kv_stream* in, const ui
   LSM_LAUNCH(filt_scan_kernel, dim3(1), dim3(1024), 0, st, a.f);
   LSM_LAUNCH(readf_seg_kernel, dim3(nseg / 4 + 1), dim3(256), 0, st, a);
   if (ntiles) LSM_LAUNCH(filt_write_kernel, dim3(uint32_t(ntiles)), dim3(256), 0, st, a.f);
-  return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
+  return launch_rc();
 }
 
 }  // extern "C"
@@ -4891,6 +4799,15 @@ int ensure_crc_tabs(lsmblk_ctx* c, hipStream_t st) {
   return LSMBLK_OK;
 }
 
+// crc_stream_kernel over up to nblk ranges: one 16-wave workgroup per CU (the replicated tables fill
+// the LDS), no more than the ranges need at four a wave.
+static int launch_crc_stream(const lsmblk_ctx* c, const CrcStreamArgs& b, uint64_t nblk, hipStream_t st) {
+  const uint64_t want = (nblk + 4 * kCsWaves - 1) / (4 * kCsWaves), cus = uint64_t(cu_count(c));
+  const uint32_t grid = uint32_t(want < cus ? (want ? want : 1) : cus);
+  LSM_LAUNCH(crc_stream_kernel, dim3(grid), dim3(64 * kCsWaves), 0, st, b);
+  return launch_rc();
+}
+
 int launch_crc(lsmblk_ctx* c, const uint8_t* blocks, const uint64_t* blk_off, uint64_t nblk, uint32_t tail,
                uint32_t* crc, uint64_t* stats, hipStream_t st, uint32_t* agg, bool sections) {
   CrcArgs a;
@@ -4902,10 +4819,8 @@ int launch_crc(lsmblk_ctx* c, const uint8_t* blocks, const uint64_t* blk_off, ui
   a.crc = crc;
   a.tabs = static_cast<const CrcTabs*>(c->crc_tabs);
   a.stats = stats;
-  const int cus = cu_count(c);
-  int per_cu = 0;
 #ifndef LSMBLK_XCRC_OLD
-  if (!agg && !sections) {  // the plain pass: one 16-wave workgroup per CU (the replicated tables fill the LDS)
+  if (!agg && !sections) {  // the plain pass
     CrcStreamArgs b;
     b.blocks = blocks;
     b.blk_off = blk_off;
@@ -4917,22 +4832,15 @@ int launch_crc(lsmblk_ctx* c, const uint8_t* blocks, const uint64_t* blk_off, ui
     b.frame_out = nullptr;
     b.sz = nullptr;
     b.dnblk = nullptr;
-    const uint64_t want = (nblk + 4 * kCsWaves - 1) / (4 * kCsWaves);
-    const uint32_t grid = uint32_t(want < uint64_t(cus) ? (want ? want : 1) : uint64_t(cus));
-    LSM_LAUNCH(crc_stream_kernel, dim3(grid), dim3(64 * kCsWaves), 0, st, b);
-    return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
+    return launch_crc_stream(c, b, nblk, st);
   }
 #endif
   // persistent: as many workgroups as are resident at once (4 KiB tables + 4 x 4 KiB staging)
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, agg ? crc_kernel<true> : crc_kernel<false>, 256, 0) !=
-          hipSuccess ||
-      per_cu < 1)
-    per_cu = 3;
-  const uint64_t want = (nblk + 3) / 4, cap = uint64_t(cus > 0 ? cus : 256) * uint64_t(per_cu);
+  const uint64_t want = (nblk + 3) / 4, cap = resident_wgs(cu_count(c), agg ? crc_kernel<true> : crc_kernel<false>, 256, 3);
   const dim3 grid(uint32_t(want < cap ? want : cap));
   if (agg) LSM_LAUNCH(crc_kernel<true>, grid, dim3(256), 0, st, a);
   else LSM_LAUNCH(crc_kernel<false>, grid, dim3(256), 0, st, a);
-  return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
+  return launch_rc();
 }
 
 // The CRCs of a framed encode's blocks, written after each block (LSMBLK_ENCODE_FRAMED): the
@@ -4950,10 +4858,6 @@ int launch_crc_frames(lsmblk_ctx* c, uint8_t* out, const uint64_t* blk_off, cons
   b.frame_out = out;
   b.sz = blk_sz;
   b.dnblk = stats;
-  const int cus = cu_count(c);
-  const uint64_t want = (nblk_max + 4 * kCsWaves - 1) / (4 * kCsWaves);
-  const uint32_t grid = uint32_t(want < uint64_t(cus) ? (want ? want : 1) : uint64_t(cus));
-  LSM_LAUNCH(crc_stream_kernel, dim3(grid), dim3(64 * kCsWaves), 0, st, b);
-  return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
+  return launch_crc_stream(c, b, nblk_max, st);
 }
 }  // namespace lsmblk_impl lsmblk_impl

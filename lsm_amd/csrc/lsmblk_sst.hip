@@ -374,6 +374,28 @@ __global__ __launch_bounds__(256) void seek_kernel(SeekArgs a) {
   or_err(a.stats, err);
 }
 
+// lsmblk_sst_files_batch's workspace: block CRCs, section offsets, data-section lengths, stats, the
+// BlockMeta sections.
+struct FilesWs {
+  uint32_t* crc;
+  uint64_t* meta_off;
+  uint64_t* data_len;
+  uint64_t* st;  // 3 x 4 stats: crc, meta, (spare)
+  uint8_t* meta;
+  uint64_t bytes;
+};
+FilesWs files_ws(uint8_t* base, uint64_t nblk, uint64_t nsst, uint64_t meta_bytes) {
+  Carve cv{base};
+  FilesWs w;
+  w.crc = cv.take<uint32_t>(nblk + 1);
+  w.meta_off = cv.take<uint64_t>(nsst + 1);
+  w.data_len = cv.take<uint64_t>(nsst + 1);
+  w.st = cv.take<uint64_t>(12);
+  w.meta = cv.take<uint8_t>(meta_bytes + 16);
+  w.bytes = cv.off;
+  return w;
+}
+
 }  // namespace
 
 extern "C" {
@@ -382,15 +404,12 @@ int lsmblk_seek_batch(lsmblk_ctx* c, const uint8_t* blocks, const uint64_t* blk_
                       const uint8_t* qkeys, const uint32_t* qkey_off, const uint32_t* q_blk, uint64_t nq, uint32_t* idx,
                       uint64_t* stats, void* stream) {
   if (!c || !blk_off || !stats || (nq && (!qkey_off || !q_blk || !idx)) || tail > 16) return LSMBLK_E_INVAL;
-  std::lock_guard<std::mutex> g(c->mu);
-  DeviceGuard dg(c->device, c);
-  if (!dg.ok) return LSMBLK_E_HIP;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(stats, 0, LSMBLK_STATS_WORDS * 8, st) != hipSuccess) return LSMBLK_E_HIP;
-  if (nq == 0) return LSMBLK_OK;
+  CallGuard call(c, stream, stats, LSMBLK_STATS_WORDS);
+  if (call.rc || nq == 0) return call.rc;
+  hipStream_t st = call.st;
   SeekArgs a{blocks, blk_off, nblk, tail, qkeys, qkey_off, q_blk, nq, idx, stats};
   LSM_LAUNCH(seek_kernel, dim3(uint32_t((nq + 255) / 256)), dim3(256), 0, st, a);
-  return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
+  return launch_rc();
 }
 
 uint32_t lsmblk_fingerprint32(const uint8_t* key, size_t klen) {
@@ -416,37 +435,13 @@ int lsmblk_sst_files_batch(lsmblk_ctx* c, const uint8_t* blocks, const uint64_t*
                            uint64_t* stats, void* stream) {
   if (!c || !blk_off || !sst_blk || !sst_ent || !kv || !kv->key_off || !file_off || !stats) return LSMBLK_E_INVAL;
   if (nsst == 0 || nblk >= 0xFFFFFFFFull || (files_cap && !files)) return LSMBLK_E_INVAL;
-  std::lock_guard<std::mutex> g(c->mu);
-  DeviceGuard dg(c->device, c);
-  if (!dg.ok) return LSMBLK_E_HIP;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  CallGuard call(c, stream, stats, LSMBLK_STATS_WORDS);
+  if (call.rc) return call.rc;
+  hipStream_t st = call.st;
   int rc;
   if ((rc = lsmblk_impl::ensure_crc_tabs(c, st))) return rc;
-  // workspace: block CRCs, BlockMeta sections, section offsets, data-section lengths, stats
-  struct Ws {
-    uint32_t* crc;
-    uint64_t* meta_off;
-    uint64_t* data_len;
-    uint64_t* st;  // 3 x 4 stats: crc, meta, (spare)
-    uint8_t* meta;
-  };
-  auto carve = [&](uint8_t* base, uint64_t meta_bytes, Ws& w) -> uint64_t {
-    uint64_t off = 0;
-    auto take = [&](uint64_t bytes) {
-      uint8_t* p = base + off;
-      off = (off + bytes + 255) & ~uint64_t(255);
-      return p;
-    };
-    w.crc = reinterpret_cast<uint32_t*>(take(4 * (nblk + 1)));
-    w.meta_off = reinterpret_cast<uint64_t*>(take(8ull * (nsst + 1)));
-    w.data_len = reinterpret_cast<uint64_t*>(take(8ull * (nsst + 1)));
-    w.st = reinterpret_cast<uint64_t*>(take(8 * 12));
-    w.meta = take(meta_bytes + 16);
-    return off;
-  };
   // a block's BlockMeta record is 24 B + its first and last keys, two distinct entries of the
   // stream (or one twice): 16 B per section + 24 B per block + twice the key arena bounds them
-  Ws w{};
   uint64_t meta_bytes = 16ull * nsst + 24ull * nblk;
   {
     uint32_t karena = 0;
@@ -454,11 +449,9 @@ int lsmblk_sst_files_batch(lsmblk_ctx* c, const uint8_t* blocks, const uint64_t*
     if (hipStreamSynchronize(st) != hipSuccess) return LSMBLK_E_HIP;
     meta_bytes += 2ull * karena;
   }
-  const uint64_t need = carve(nullptr, meta_bytes, w);
-  if (need > c->sws_cap && (rc = grow(st, &c->sws, &c->sws_cap, need, 1))) return rc;
-  carve(c->sws, meta_bytes, w);
+  if ((rc = c->sws.grow(st, files_ws(nullptr, nblk, nsst, meta_bytes).bytes, 1))) return rc;
+  const FilesWs w = files_ws(c->sws, nblk, nsst, meta_bytes);
   if (hipMemsetAsync(w.st, 0, 8 * 12, st) != hipSuccess) return LSMBLK_E_HIP;
-  if (hipMemsetAsync(stats, 0, LSMBLK_STATS_WORDS * 8, st) != hipSuccess) return LSMBLK_E_HIP;
   if (nblk && (rc = lsmblk_impl::launch_crc(c, blocks, blk_off, nblk, 0, w.crc, w.st, st))) return rc;
   if ((rc = lsmblk_impl::block_meta_locked(c, blocks, blk_off, nblk, 0, sst_blk, nsst, w.meta, meta_bytes + 16,
                                            w.meta_off, w.st + 4, st)))
@@ -488,7 +481,7 @@ int lsmblk_sst_files_batch(lsmblk_ctx* c, const uint8_t* blocks, const uint64_t*
   if (nblk) LSM_LAUNCH(sst_data_kernel, dim3(uint32_t((nblk + 3) / 4)), dim3(256), 0, st, a);
   LSM_LAUNCH(sst_meta_kernel, dim3((nsst + 3) / 4), dim3(256), 0, st, a);
   LSM_LAUNCH(sst_bloom_kernel, dim3(nsst), dim3(256), 0, st, a);
-  return hipGetLastError() == hipSuccess ? LSMBLK_OK : LSMBLK_E_HIP;
+  return launch_rc();
 }
 
 }  // extern "C"
