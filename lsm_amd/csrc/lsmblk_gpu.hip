@@ -76,6 +76,8 @@ __device__ __forceinline__ void dbg_trace(uint64_t* dbg, uint64_t t, uint32_t k)
 // LDS reads per lane issued together before their uses (one LDS round trip per batch instead
 // of one per read): flushes, value copies, chunk moves.
 constexpr uint32_t kLB = 2;  // decode: 2 measured 1 % faster per step than 1, 4 slower (1.64 vs 1.58 ms)
+// Chunk groups per batch of the decode's in-place value moves (as kEBBlock).
+constexpr uint32_t kDecMB = 2;
 #ifndef LSMBLK_XEB
 #define LSMBLK_XEB 4
 #endif
@@ -89,18 +91,30 @@ constexpr uint32_t kEB = LSMBLK_XEB;
 constexpr uint32_t kEBBlock = 2;
 
 
-// LDS per single-wave workgroup is exactly 8 KiB, so 20 blocks are resident per CU (5 waves per
-// SIMD; 10.3 KiB gave 15).  A 4 KiB block (up to 4098 B: the builder overshoots by 2) at any
-// 16-B lead, plus the 16-B staging round-up, fits the image.
-constexpr uint32_t kDecImg = 4128;  // staged block bytes per wave
-constexpr uint32_t kDecMaxE = 128;  // entries of a fast-path block (tables in registers, 2 per lane)
-constexpr uint32_t kDecOut = 4032;  // LDS output image (keys + values) of a fast-path block
+// LDS per single-wave workgroup is 6 816 B: room for 24 blocks per CU (8 KiB gave 20, 10.3 KiB
+// 15).  The registers do not follow yet, so 20 are resident: both decode kernels are built for 5
+// waves per SIMD (amdgpu_waves_per_eu(5): 92 and 95 VGPRs, no scratch; left alone the lagged one
+// took 97, 4 waves per SIMD, and under (6) both spill -- DESIGN.md section 4).  A 4 KiB block (up
+// to 4098 B: the builder overshoots by 2) at any 16-B lead, plus the 16-B staging round-up, fits
+// the image.  The decoded value run is compacted inside the image (dec_fast_outputs), so only the
+// key run needs an image of its own.
+constexpr uint32_t kDecImg = 4128;     // staged block bytes per wave
+constexpr uint32_t kDecMaxE = 128;     // entries of a fast-path block (tables in registers, 2 per lane)
+constexpr uint32_t kDecKeyImg = 2176;  // LDS image of a fast-path block's decoded key run
+constexpr uint32_t kDecMapN = 256;     // 16-B chunks of the in-place value run that the chunk map covers
+// Most decoded bytes (key run + value run, each in whole 16-B chunks) of a block that takes the
+// LDS route: the size of the former combined output image, kept as the route's bound so that no
+// block that went straight to global memory before is compacted now (tests/path_cases.py and
+// tests/decode_cases.py build their blocks around it).  It also keeps the value run inside the map.
+constexpr uint32_t kDecOut = 4032;
+static_assert(kDecOut <= 16 * kDecMapN && 16 * kDecMapN <= kDecImg, "the chunk map covers the value run");
 
 struct alignas(16) DecLds {
   uint8_t img[kDecImg];
-  alignas(16) uint8_t out[kDecOut];  // decoded key run, then (16-B aligned) value run
+  alignas(16) uint8_t kimg[kDecKeyImg];  // decoded key run (mirrors the global 16-B alignment)
+  alignas(16) uint16_t cmap[kDecMapN];   // value-run chunk -> its source byte in img, 0 = an edge chunk
 };
-static_assert(sizeof(DecLds) == 8160, "decode LDS: 20 blocks per CU");
+static_assert(sizeof(DecLds) <= (160 << 10) / 24, "decode LDS: room for 24 blocks per CU");
 
 // Entry tables of a large block (kDecMaxE entries at a time).  A large block is not staged, so
 // the tables live in the unused image.
@@ -183,10 +197,27 @@ __device__ __forceinline__ void st_short(const rsrc_t& R, uint32_t off, uint32_t
   }
 }
 
-// Output sinks of the lane-per-entry decode: unaligned runs either go straight to global
-// memory (GlbSink, buffer stores) or are composed in the wave's LDS output image (LdsSink)
-// that is then flushed with aligned, coalesced 16-B stores (one HBM write request per 64-B
-// line instead of one per lane).
+// bytes [0, len) (len < 16) of v at an unaligned LDS address: overlapping stores of the widest
+// size that fits (8 + 8, 4 + 4, or single bytes)
+__device__ __forceinline__ void lds_st_short(uint8_t* p, uint32_t len, const uint32_t (&v)[4]) {
+  if (len >= 8) {
+    const uint32_t x = len - 8, sh = x & 3;
+    const uint32_t w0 = x < 4 ? v[0] : v[1], w1 = x < 4 ? v[1] : v[2], w2 = x < 4 ? v[2] : v[3];
+    *reinterpret_cast<u32x2*>(p) = u32x2{v[0], v[1]};
+    *reinterpret_cast<u32x2*>(p + x) = u32x2{__builtin_amdgcn_alignbyte(w1, w0, sh), __builtin_amdgcn_alignbyte(w2, w1, sh)};
+  } else if (len >= 4) {
+    *reinterpret_cast<uint32_t*>(p) = v[0];
+    *reinterpret_cast<uint32_t*>(p + len - 4) = __builtin_amdgcn_alignbyte(v[1], v[0], len - 4);
+  } else {
+    for (uint32_t i = 0; i < len; ++i) p[i] = uint8_t(v[0] >> (8 * i));
+  }
+}
+
+// Output sinks of the lane-per-entry decode.  GlbSink: the unaligned key and value runs go
+// straight to global memory (buffer stores).  LdsSink: the key run is composed in the wave's
+// LDS key image and the value run is compacted inside the staged block (dec_fast_outputs); both
+// are then flushed with aligned, coalesced 16-B stores (one HBM write request per 64-B line
+// instead of one per lane).
 struct GlbSink {
   rsrc_t RK, RV;
   uint32_t kb, vb;  // byte of the first key / value in its descriptor (16-B aligned base)
@@ -198,52 +229,35 @@ struct GlbSink {
   }
 };
 struct LdsSink {
-  uint8_t* out;
-  uint32_t kb, vb;  // LDS byte of the first key / value
-  __device__ __forceinline__ void put16(bool val, uint32_t off, const uint32_t (&v)[4]) const {
-    *reinterpret_cast<u32x4*>(out + (val ? vb : kb) + off) = u32x4{v[0], v[1], v[2], v[3]};
+  uint8_t* kimg;   // the key image
+  uint32_t kb;     // its byte of the first key
+  uint16_t* cmap;  // the chunk map of the value run compacted inside the staged block
+  uint32_t vb;     // block-image byte of the first compacted value
+  __device__ __forceinline__ void put16(bool, uint32_t off, const uint32_t (&v)[4]) const {  // (keys only)
+    *reinterpret_cast<u32x4*>(kimg + kb + off) = u32x4{v[0], v[1], v[2], v[3]};
   }
-  __device__ __forceinline__ void put_short(bool val, uint32_t off, uint32_t len, const uint32_t (&v)[4]) const {
-    uint8_t* p = out + (val ? vb : kb) + off;
-    if (len >= 8) {
-      const uint32_t x = len - 8, sh = x & 3;
-      const uint32_t w0 = x < 4 ? v[0] : v[1], w1 = x < 4 ? v[1] : v[2], w2 = x < 4 ? v[2] : v[3];
-      *reinterpret_cast<u32x2*>(p) = u32x2{v[0], v[1]};
-      *reinterpret_cast<u32x2*>(p + x) =
-          u32x2{__builtin_amdgcn_alignbyte(w1, w0, sh), __builtin_amdgcn_alignbyte(w2, w1, sh)};
-    } else if (len >= 4) {
-      *reinterpret_cast<uint32_t*>(p) = v[0];
-      *reinterpret_cast<uint32_t*>(p + len - 4) = __builtin_amdgcn_alignbyte(v[1], v[0], len - 4);
-    } else {
-      for (uint32_t i = 0; i < len; ++i) p[i] = uint8_t(v[0] >> (8 * i));
-    }
+  __device__ __forceinline__ void put_short(bool, uint32_t off, uint32_t len, const uint32_t (&v)[4]) const {
+    lds_st_short(kimg + kb + off, len, v);
   }
 };
 
-// Value copies of a staged (LDS) wave as 16-B-aligned output chunks, each funnel-shifted from
-// 8-B-aligned image reads (LSMBLK_XDEC_VALN, round 6; 0 = the unaligned 16-B pieces below).
-// PMC at U (profiles/r06_pmc_lds_decode_{old,new}.txt): unaligned-LDS stall cycles 8.2e8 -> 3.6e8,
-// LDS issue waits 4.7e8 -> 1.2e8 (0.60 -> 0.20 of all instruction waits), bank conflicts 2.2e7 ->
-// 3.0e8 (the staged values sit at a ~128-B stride, so lanes reading the same chunk of their values
-// share banks), VALU +46 %; decode 2.050 against 2.060 ms (three alternating pairs, one box).
-// Rotating each lane's chunk order spreads the banks (1.2e8) but its VALU made the kernel 2-6 %
-// slower (not kept).
-#ifndef LSMBLK_XDEC_VALN
-#define LSMBLK_XDEC_VALN 1
-#endif
-// Fast path, lane per entry: every entry lane writes its own key and value as contiguous
-// runs of 16-B pieces (the last piece overlaps the previous one), so runs of adjacent
-// entries abut and no lane needs a chunk -> entry search.
+// Fast path, lane per entry: every entry lane writes its own key (and, to a GlbSink, its value)
+// as a contiguous run of 16-B pieces (the last piece overlaps the previous one), so runs of
+// adjacent entries abut and no lane needs a chunk -> entry search.
 // The piece loops run a wave-uniform trip count (the wave's longest run) with each lane's piece
 // index clamped to its last piece, so no per-piece exec mask is needed (PMC: the scalar unit,
 // which runs those masks, is the decode's busiest pipe).  Lanes past the block's entries are
 // masked off once per iteration (mirroring lane 0's entry instead made up to 63 lanes write the
 // same LDS words: bank-conflicted, the decode lost a third of its rate).  Keys under 16 B,
 // suffixes before the image start and values under 16 B keep per-lane paths.
+// To an LdsSink a value is not copied here: its lane keeps the value's first and last 16 bytes
+// (eh, et: the bytes of the run's chunks shared between values) and enters every chunk of the
+// compacted run lying wholly inside the value in the chunk map (dec_fast_outputs moves those).
 template <class Sink>
 __device__ __forceinline__ void dec_entry_runs(const DecodeArgs& a, DecLds& L, uint32_t lead, uint32_t n,
                                                const DecEnt (&ent)[2], uint64_t E0, uint64_t K0, uint64_t V0,
-                                               const Sink& out, uint32_t skip) {
+                                               const Sink& out, uint32_t skip, uint32_t (&eh)[2][4],
+                                               uint32_t (&et)[2][4]) {
   const uint32_t l = lane_id();
   const uint8_t* img = L.img;
   const uint32_t fk = lead + 4;  // image byte of the first key
@@ -260,28 +274,9 @@ __device__ __forceinline__ void dec_entry_runs(const DecodeArgs& a, DecLds& L, u
     const bool kirr = live && (kl < 16 || sb < p);
     const bool kuni = !__ballot(kirr);
     const uint32_t nkmax = __builtin_amdgcn_readlane(wave_incl_max32(live ? (kl + 15) >> 4 : 0u), 63);
-    const uint32_t nvmax = __builtin_amdgcn_readlane(wave_incl_max32(live && vl >= 16 ? (vl + 15) >> 4 : 0u), 63);
-    // Aligned value path (values composed in the LDS output image, at most 64 entries, every value
-    // >= 16 B): lane k writes the 16-B-aligned image chunks that start inside its value, each built
-    // from 8-B-aligned reads of the staged image and a byte funnel shift; the chunk that runs past
-    // the value's end takes the rest from the next value (lane k + 1).  The misaligned 16-B LDS reads
-    // and writes of the piece copies below cost the LDS array extra passes (PMC SQ_LDS_UNALIGNED_STALL;
-    // the same accesses moved to aligned addresses, a timing probe: decode 2.14 -> 1.96 ms at U).
-    const uint32_t vS = sb + s + 10, vD = out.vb + vout;  // the value's image / output-image bytes
-    bool valn = false;
-    uint32_t vm = 0, vmmax = 0, vS1 = 0, vD1 = 0;
-    if constexpr (std::is_same_v<Sink, LdsSink>) {
-      // (lane 0 also writes the chunk holding the run's first byte, read from vS - (vD & 15) on)
-      valn = LSMBLK_XDEC_VALN && it == 0 && n <= 64 && !__ballot(live && (vl < 16 || (l == 0 && vS < (vD & 15)))) &&
-             !(skip & (4 | 32 | 64));
-      if (valn) {  // (wave-uniform)
-        const uint32_t cs = l == 0 ? (vD >> 4) : ((vD + 15) >> 4), ce = (vD + vl - 1) >> 4;
-        vm = live ? ce - cs + 1 : 0u;
-        vmmax = __builtin_amdgcn_readlane(wave_incl_max32(vm), 63);
-        vS1 = uint32_t(__shfl(int(vS), int(min(l + 1, 63u)), 64));
-        vD1 = uint32_t(__shfl(int(vD), int(min(l + 1, 63u)), 64));
-      }
-    }
+    uint32_t nvmax = 0;
+    if constexpr (!std::is_same_v<Sink, LdsSink>)
+      nvmax = __builtin_amdgcn_readlane(wave_incl_max32(live && vl >= 16 ? (vl + 15) >> 4 : 0u), 63);
     if (!live) continue;
     if (!(skip & 8)) {
       const uint64_t e = E0 + k;
@@ -333,58 +328,18 @@ __device__ __forceinline__ void dec_entry_runs(const DecodeArgs& a, DecLds& L, u
         }
       }
     }
-    if (valn) {
-      uint8_t* const ob = L.out;
-      // 16 bytes of the staged image at byte x (any alignment) from the 8-B-aligned dwords d[0..5]
-      // that start at x & ~7: a dword select by bit 2, then v_alignbyte by x & 3
-      // (the dword select by mask, not `b2 ? d[j + 1] : d[j]`: the compiler turned that into a
-      // dynamically indexed array in scratch memory -- decode 3.35 ms)
-      auto funnel = [](const uint32_t (&d)[6], uint32_t x, uint32_t (&v)[4]) {
-        const uint32_t m = (x & 4) ? ~0u : 0u;
-        uint32_t y[5];
-#pragma unroll
-        for (uint32_t j = 0; j < 5; ++j) y[j] = __builtin_amdgcn_bitop3_b32(m, d[j + 1], d[j], 0xCA);  // m ? d[j + 1] : d[j]
-#pragma unroll
-        for (uint32_t i = 0; i < 4; ++i) v[i] = __builtin_amdgcn_alignbyte(y[i + 1], y[i], x & 3);
-      };
-      auto rd8 = [&](uint32_t x, uint32_t& lo, uint32_t& hi) {  // (x 8-B aligned)
-        const u32x2 q = *reinterpret_cast<const u32x2*>(img + x);
-        lo = q.x, hi = q.y;
-      };
-      const uint32_t cs = l == 0 ? (vD >> 4) : ((vD + 15) >> 4);
-      const uint32_t a0 = vS + 16 * cs - vD;  // image byte of chunk cs's first byte (>= 0, see valn)
-      uint32_t d[6], x8 = a0 & ~7u;
-      rd8(x8, d[0], d[1]);
-      rd8(x8 + 8, d[2], d[3]);
-      rd8(x8 + 16, d[4], d[5]);
-      for (uint32_t i = 0; i < vmmax; ++i) {
-        if (i < vm) {
-          uint32_t v[4];
-          funnel(d, a0, v);
-          const uint32_t c = cs + i, cut = vD + vl - 16 * c;  // bytes of the chunk from this value
-          if (cut < 16 && k + 1 < n) {  // the rest from the next value
-            const uint32_t a1 = vS1 + 16 * c - vD1, y8 = a1 & ~7u;
-            uint32_t e[6], w[4];
-            rd8(y8, e[0], e[1]);
-            rd8(y8 + 8, e[2], e[3]);
-            rd8(y8 + 16, e[4], e[5]);
-            funnel(e, a1, w);
-#pragma unroll
-            for (uint32_t q = 0; q < 4; ++q) {
-              const int32_t nb = int32_t(cut) - int32_t(4 * q);  // leading bytes of dword q from this value
-              const uint32_t msk = nb <= 0 ? 0u : nb >= 4 ? ~0u : (1u << (8 * nb)) - 1;
-              v[q] = (v[q] & msk) | (w[q] & ~msk);
-            }
-          }
-          *reinterpret_cast<u32x4*>(ob + 16 * c) = u32x4{v[0], v[1], v[2], v[3]};
-          d[0] = d[4], d[1] = d[5];
-          x8 += 16;
-          rd8(x8 + 8, d[2], d[3]);
-          rd8(x8 + 16, d[4], d[5]);
-        }
+    const uint32_t src = sb + s + 10;  // image byte of the value
+    if constexpr (std::is_same_v<Sink, LdsSink>) {
+      if (vl && !(skip & 4)) {
+        // (a 16-B read of a shorter value ends inside the image: the value ends at least 2 bytes before
+        // the block does, and the image holds 15 bytes past the block)
+        lds_read16(img, src, eh[it]);
+        lds_read16(img, src + (vl > 16 ? vl - 16 : 0u), et[it]);
+        const uint32_t vD = out.vb + vout;  // image byte of the compacted value
+        const uint32_t d = src - vD;        // + compacted byte = staged byte
+        for (uint32_t c = (vD + 15) >> 4; 16 * c + 16 <= vD + vl; ++c) out.cmap[c] = uint16_t(d + 16 * c);
       }
     } else if (!(skip & 4)) {
-      const uint32_t src = sb + s + 10;  // image byte of the value
       if (vl >= 16) {
         for (uint32_t i0 = 0; i0 < nvmax; i0 += kLB) {  // uniform trip count, pieces clamped
           u32x4 q[kLB];
@@ -449,17 +404,91 @@ __device__ __forceinline__ void flush_run_masked(uint8_t* gdst_aligned, const ui
 __device__ void dec_fast_outputs(const DecodeArgs& a, DecLds& L, uint32_t lead, const BlockHdr& h,
                                  const DecEnt (&ent)[2], uint64_t E0, uint64_t K0, uint64_t V0, uint32_t K,
                                  uint32_t V, uint32_t skip) {
+  const uint32_t l = lane_id();
+  const uint32_t n = h.n;
   const uint32_t kb = uint32_t(K0 & 15), vb = uint32_t(V0 & 15);
-  const uint32_t vrun = (kb + K + 15) & ~15u;  // LDS start of the value run's first chunk
-  // the flush reads whole 16-B chunks: the value run's last chunk must lie in the image
-  if (vrun + ((vb + V + 15) & ~15u) <= kDecOut) {
-    dec_entry_runs(a, L, lead, h.n, ent, E0, K0, V0, LdsSink{L.out, kb, vrun + vb}, skip);
+  // d_k = (image byte of value k) - (image byte of its place in the compacted run), in entry order.
+  // The in-place route needs 0 <= d_0 <= d_1 <= ...: the values lie in the block in entry order
+  // without overlap, each at or above its place.  Blocks from the encoder always do:
+  //   * d_0 >= 0.  Value 0 starts at image byte lead + off_0 + 14 + s_0 and goes to vb <= 15.  An
+  //     entry at block offset 0 is the first key's own, and the parse rules (p <= its own s,
+  //     p + s > 0) give it s >= 1, so the value starts at byte 15 or above.  Tight at lead = 0,
+  //     vb = 15 and a first key of one byte: d_0 = 0, the value stays where it is.
+  //   * d_k - d_(k-1) = 14 + s_k, the header, suffix, ts and length that lie between the values.
+  // The offsets table may also name the entries in any order, or the same entry twice, and such a
+  // block is well-formed: it fails the test and goes through the GlbSink.
+  int32_t dprev = 0;
+  bool mono = true;
+#pragma unroll
+  for (uint32_t it = 0; it < 2; ++it) {
+    if (64 * it >= n) break;
+    const bool live = 64 * it + l < n;
+    const int32_t d = live ? int32_t(lead + ent[it].epos + 14 + ent[it].s) - int32_t(vb + ent[it].vout) : 0x7FFFFFFF;
+    const int32_t up = __shfl_up(d, 1, 64);
+    mono = mono && d >= (l ? up : dprev);
+    dprev = __builtin_amdgcn_readlane(d, 63);
+  }
+  // the flushes read whole 16-B chunks: the key run's last chunk must lie in the key image, the
+  // value run's in the block image (kDecOut).  (A key run over kDecKeyImg that fitted the former
+  // combined image with few value bytes took the LDS route before and takes the GlbSink now.)
+  const uint32_t krun = (kb + K + 15) & ~15u;
+  if (!__ballot(!mono) && krun <= kDecKeyImg && krun + ((vb + V + 15) & ~15u) <= kDecOut) {
+    static_assert(sizeof(DecLds::cmap) == 32 * 16, "the map is zeroed by 32 lanes");
+    if (l < 32) reinterpret_cast<u32x4*>(L.cmap)[l] = u32x4{0, 0, 0, 0};
     wave_sync();
-    flush_run(a.keys + (K0 - kb), L.out, kb, K);
-    flush_run(a.vals + (V0 - vb), L.out + vrun, vb, V);
+    // 1. ts and offsets out, the key run into the key image, every value's two ends into registers,
+    //    the chunk map -- everything that reads the block where the compaction will write
+    uint32_t eh[2][4] = {}, et[2][4] = {};
+    dec_entry_runs(a, L, lead, n, ent, E0, K0, V0, LdsSink{L.kimg, kb, L.cmap, vb}, skip, eh, et);
+    wave_sync();
+    flush_run(a.keys + (K0 - kb), L.kimg, kb, K);
+    // 2. The chunks lying wholly inside one value move down to image byte vb + (value offset), a
+    //    lane per destination chunk, in ascending batches of 64 kDecMB chunks, all of a batch's
+    //    reads issued before its writes (one wave: its LDS accesses complete in issue order).
+    //    No source is overwritten unread: chunk c of value k is read at 16 c + d_k, so (d_k >= 0)
+    //    at or above where it is written, and (d_k ascending) every chunk of a later batch is read
+    //    at or above its own destination, which is at or above this batch's end.
+    if (!(skip & 4)) {
+      const uint32_t nw = (vb + V) >> 4;  // chunks below nw are whole
+      for (uint32_t c0 = 0; c0 < nw; c0 += 64 * kDecMB) {
+        uint32_t src[kDecMB] = {};
+        u32x4 v[kDecMB] = {};
+#pragma unroll
+        for (uint32_t j = 0; j < kDecMB; ++j) {
+          const uint32_t c = c0 + 64 * j + l;
+          src[j] = c < nw ? L.cmap[c] : 0u;
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < kDecMB; ++j)
+          if (src[j]) v[j] = *reinterpret_cast<const u32x4*>(L.img + src[j]);
+#pragma unroll
+        for (uint32_t j = 0; j < kDecMB; ++j)
+          if (src[j]) *reinterpret_cast<u32x4*>(L.img + 16 * (c0 + 64 * j + l)) = v[j];
+      }
+      wave_sync();
+      // 3. The chunks shared between values, from the entry lanes' registers: a value of 16 bytes or
+      //    more rewrites its first and last 16 (what lies inside whole chunks with the bytes the
+      //    move put there), a shorter one is written whole.
+#pragma unroll
+      for (uint32_t it = 0; it < 2; ++it) {
+        if (64 * it >= n) break;
+        const uint32_t vl = ent[it].vl;
+        uint8_t* const o = L.img + vb + ent[it].vout;
+        if (64 * it + l >= n) continue;
+        if (vl >= 16) {
+          *reinterpret_cast<u32x4*>(o) = u32x4{eh[it][0], eh[it][1], eh[it][2], eh[it][3]};
+          *reinterpret_cast<u32x4*>(o + vl - 16) = u32x4{et[it][0], et[it][1], et[it][2], et[it][3]};
+        } else if (vl) {
+          lds_st_short(o, vl, eh[it]);
+        }
+      }
+      wave_sync();
+      flush_run(a.vals + (V0 - vb), L.img, vb, V);
+    }
   } else {
     const GlbSink g{make_rsrc_exact(a.keys + (K0 - kb), kb + K), make_rsrc_exact(a.vals + (V0 - vb), vb + V), kb, vb};
-    dec_entry_runs(a, L, lead, h.n, ent, E0, K0, V0, g, skip);
+    uint32_t eh[2][4], et[2][4];  // (unused)
+    dec_entry_runs(a, L, lead, n, ent, E0, K0, V0, g, skip, eh, et);
   }
 }
 
@@ -562,7 +591,7 @@ __device__ __forceinline__ void copy_run_wave(const rsrc_t& RS, uint32_t so, con
 // lanes' first-piece numbers with 6 dependent ds_bpermutes and read the owner's fields with 4
 // more; the copies are most of M's large-block encode.)
 constexpr uint32_t kCopyScratch = 4 * 64 + 64;
-static_assert(4 * kCopyScratch <= kDecOut, "the decode's large-block path lends its output image");
+static_assert(4 * kCopyScratch <= kDecKeyImg, "the decode's large-block path lends its key image");
 
 template <uint32_t B>
 struct CopyBatch {
@@ -571,10 +600,21 @@ struct CopyBatch {
 };
 
 // Rows g0 .. g0 + 64 B of the piece numbering: owners, then the pieces' loads.
-template <uint32_t B>
+// PIN (the decode's large-block path): the batch's registers are claimed before any address is
+// worked out and the loads are issued by inline asm into them.  Left to itself the register
+// allocator may use a load's destination registers as scratch for its address arithmetic; they
+// are also the data of the previous round's stores, a VALU write to them must wait for those
+// (vmcnt), and that wait, in front of every load, also waits for the load before it: one load in
+// flight instead of B (it happened with the in-place fast path beside this code: config M's decode
+// 1.94 -> 2.06 ms).  The caller lands the loads (copy_land) before it stores.
+template <uint32_t B, bool PIN = false>
 __device__ __forceinline__ void copy_issue(const rsrc_t& RS, uint32_t g0, uint32_t total, uint32_t np, uint32_t first,
                                            uint32_t* sc, uint32_t& carry, CopyBatch<B>& c) {
   const uint32_t l = lane_id();
+  if constexpr (PIN) {
+#pragma unroll
+    for (uint32_t j = 0; j < B; ++j) asm volatile("" : "=v"(c.q[j]));  // (no instruction: claims the registers)
+  }
   const u32x4* rec = reinterpret_cast<const u32x4*>(sc);
   uint32_t* mark = sc + 4 * 64;
   uint32_t own[B];
@@ -600,10 +640,26 @@ __device__ __forceinline__ void copy_issue(const rsrc_t& RS, uint32_t g0, uint32
     if (g < total) {
       const u32x4 r = rec[own[j]];
       const uint32_t off = min(16 * (g - r.w), r.z);
-      c.q[j] = gload16(RS, r.x + off);
+      const uint32_t src = r.x + off;
+      if constexpr (PIN) {
+        // (s_nop 4 once: a VALU write of RS's SGPRs needs 5 wait states before a VMEM read of them,
+        // which the compiler's hazard pass does not check inside asm)
+        if (j == 0) asm volatile("s_nop 4\n\tbuffer_load_dwordx4 %0, %1, %2, 0 offen" : "+v"(c.q[j]) : "v"(src), "s"(RS));
+        else asm volatile("buffer_load_dwordx4 %0, %1, %2, 0 offen" : "+v"(c.q[j]) : "v"(src), "s"(RS));
+      } else {
+        c.q[j] = gload16(RS, src);
+      }
       c.dst[j] = r.y + off;
     }
   }
+}
+
+// The asm loads of copy_issue<B, true> have landed (the compiler does not count them).
+template <uint32_t B>
+__device__ __forceinline__ void copy_land(CopyBatch<B>& c) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#pragma unroll
+  for (uint32_t j = 0; j < B; ++j) asm volatile("" : "+v"(c.q[j]));  // defined here for the compiler
 }
 
 template <uint32_t B>
@@ -622,7 +678,7 @@ __device__ __forceinline__ void copy_store(const rsrc_t& RD, const CopyBatch<B>&
 struct NoAfter {
   __device__ void operator()(uint32_t, uint32_t, uint32_t) const {}
 };
-template <uint32_t B = kBigB, class After = NoAfter>
+template <uint32_t B = kBigB, bool PIN = false, class After = NoAfter>
 __device__ __forceinline__ void copy_long_runs(bool longrun, const rsrc_t& RS, uint32_t so, const rsrc_t& RD,
                                                uint32_t dof, uint32_t len, uint32_t* sc, const After& after = After()) {
   const uint32_t l = lane_id();
@@ -639,7 +695,8 @@ __device__ __forceinline__ void copy_long_runs(bool longrun, const rsrc_t& RS, u
   uint32_t carry = 0;  // owner + 1 of the previous row's last piece
   for (uint32_t g0 = 0; g0 < total; g0 += 64 * B) {
     CopyBatch<B> c;
-    copy_issue(RS, g0, total, np, first, sc, carry, c);
+    copy_issue<B, PIN>(RS, g0, total, np, first, sc, carry, c);
+    if constexpr (PIN) copy_land(c);
     copy_store(RD, c);
     after(first, g0, g0 + 64 * B >= total ? ~0u : g0 + 64 * B);
   }
@@ -712,7 +769,7 @@ __device__ void dec_big_outputs(const DecodeArgs& a, const DecTables& L, const r
       vl = L.vout[k + 1] - L.vout[k];
       if (vl < kCoop) copy_run(R, vsrc, lim, RV, vdst, vl);
     }
-    copy_long_runs<kDecBigB>(live && vl >= kCoop, R, vsrc, RV, vdst, vl, sc);
+    copy_long_runs<kDecBigB, true>(live && vl >= kCoop, R, vsrc, RV, vdst, vl, sc);
   }
 }
 
@@ -918,7 +975,7 @@ __device__ void decode_block(const DecodeArgs& a, DecLds& L, uint64_t b, uint64_
     if (fast) {
       dec_fast_outputs(a, L, lead, h, ent, E0, K0, V0, uint32_t(K), uint32_t(V), diag_mask(a.skip));
     } else if (big && h.n <= kDecMaxE) {
-      dec_big_outputs(a, T, R, lead, h, h.n, E0, K0, V0, uint32_t(K), uint32_t(V), reinterpret_cast<uint32_t*>(L.out));
+      dec_big_outputs(a, T, R, lead, h, h.n, E0, K0, V0, uint32_t(K), uint32_t(V), reinterpret_cast<uint32_t*>(L.kimg));
     } else if (big) {
       uint64_t kr = 0, vr = 0;
       for (uint32_t c0 = 0; c0 < h.n; c0 += kDecMaxE) {
@@ -926,7 +983,7 @@ __device__ void decode_block(const DecodeArgs& a, DecLds& L, uint64_t b, uint64_
         wave_sync();  // the previous chunk's table reads are done
         parse_tables(GlbImg{R, lead}, c0, nc, kr, vr);
         wave_sync();
-        dec_big_outputs(a, T, R, lead, h, nc, E0 + c0, K0, V0, uint32_t(K), uint32_t(V), reinterpret_cast<uint32_t*>(L.out));
+        dec_big_outputs(a, T, R, lead, h, nc, E0 + c0, K0, V0, uint32_t(K), uint32_t(V), reinterpret_cast<uint32_t*>(L.kimg));
       }
     } else if (fits) {
       dec_simple_outputs(a, LdsImg{L.img, lead}, h, E0, K0, V0);
@@ -937,11 +994,10 @@ __device__ void decode_block(const DecodeArgs& a, DecLds& L, uint64_t b, uint64_
   raise_err(a.stats, err);
 }
 
-// One wave per block, no inter-wave waiting: the bases come from the count + scan passes.
-// One single-wave workgroup per block (LDS, not waves, bounds the residency: single-wave
-// workgroups pack the CU's LDS best).  No inter-wave waiting: the output bases come from the
-// count + scan passes.
-__global__ __launch_bounds__(64) void decode_kernel(DecodeArgs a) {
+// One single-wave workgroup per block (single-wave workgroups pack the CU's LDS best; since the
+// in-place compaction the registers, 5 waves per SIMD, bound the residency at 20 per CU, the LDS
+// would hold 24).  No inter-wave waiting: the output bases come from the count + scan passes.
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void decode_kernel(DecodeArgs a) {
   __shared__ DecLds lds;
   const uint64_t b = blockIdx.x;
   decode_block<false>(a, lds, b, uni64(a.blk_off[b]), uni64(a.blk_off[b + 1]), [] {}, [] {}, [] {});
@@ -1134,7 +1190,7 @@ __device__ void lag_tile_finish(const DecodeArgs& a, uint64_t t, uint32_t& err, 
   }
 }
 
-__global__ __launch_bounds__(64) void decode_lag_kernel(DecodeArgs a) {
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void decode_lag_kernel(DecodeArgs a) {
   __shared__ DecLds lds;
   // Workgroup indices, the lag and the block count are below 2^31 (lsmblk_decode_batch_ex), so the
   // per-workgroup bookkeeping is 32-bit: the scalar unit, not the vector one, is the decode's most
@@ -2067,22 +2123,6 @@ __device__ __forceinline__ u32x4 rec_get(const EmitBlockLds&, const EmitRecReg& 
 // entry k's record start in the block (the offsets table's value)
 __device__ __forceinline__ uint32_t rec_pos(const EmitLds& L, const EmitRecLds&, uint32_t, uint32_t k) { return L.erec[4 * k] & 0xFFFF; }
 __device__ __forceinline__ uint32_t rec_pos(const EmitBlockLds&, const EmitRecReg& R, uint32_t it, uint32_t) { return R.x[it] & 0xFFFF; }
-
-// bytes [0, len) (len < 16) of v at an unaligned LDS address: overlapping stores of the widest
-// size that fits (8 + 8, 4 + 4, or single bytes)
-__device__ __forceinline__ void lds_st_short(uint8_t* p, uint32_t len, const uint32_t (&v)[4]) {
-  if (len >= 8) {
-    const uint32_t x = len - 8, sh = x & 3;
-    const uint32_t w0 = x < 4 ? v[0] : v[1], w1 = x < 4 ? v[1] : v[2], w2 = x < 4 ? v[2] : v[3];
-    *reinterpret_cast<u32x2*>(p) = u32x2{v[0], v[1]};
-    *reinterpret_cast<u32x2*>(p + x) = u32x2{__builtin_amdgcn_alignbyte(w1, w0, sh), __builtin_amdgcn_alignbyte(w2, w1, sh)};
-  } else if (len >= 4) {
-    *reinterpret_cast<uint32_t*>(p) = v[0];
-    *reinterpret_cast<uint32_t*>(p + len - 4) = __builtin_amdgcn_alignbyte(v[1], v[0], len - 4);
-  } else {
-    for (uint32_t i = 0; i < len; ++i) p[i] = uint8_t(v[0] >> (8 * i));
-  }
-}
 
 #ifndef LSMBLK_XEBB
 #define LSMBLK_XEBB 4
