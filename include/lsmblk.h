@@ -484,8 +484,11 @@ int lsmblk_compact_merge_batch_ex(lsmblk_ctx* ctx, const lsmblk_kv_stream* in, c
 /* Rotation state of one range over `ext` = its n_own kept entries followed by the halo (ext->n
  * entries in all).  flags: LSMBLK_SHARD_LAST when ext ends where the whole compaction's stream ends
  * (the last rank, or a halo that reached the end).  sst_cap bounds the SSTs that start in the range.
- * The state stays on the context for the next two calls (same context, no other compaction call on
- * it in between).  Asynchronous. */
+ * The state stays on the context until the next prepare: lsmblk_shard_rotation_carry and
+ * lsmblk_shard_encode_batch may follow any number of times, each encode using the latest carry (same
+ * context, no other compaction call on it in between).  Without LSMBLK_SHARD_LAST the halo must reach
+ * the first block start or SST start at or after n_own: a shorter one, and no halo at all
+ * (ext->n == n_own) under a carry_in.p below n_own, reports LSMBLK_ERR_SEGMENTS.  Asynchronous. */
 #define LSMBLK_SHARD_LAST 1u
 int lsmblk_shard_rotation_prepare(lsmblk_ctx* ctx, const lsmblk_kv_stream* ext, uint64_t n_own, uint32_t flags,
                                   uint32_t block_size, uint64_t target_sst_size, uint32_t sst_cap, void* stream);
@@ -506,7 +509,9 @@ int lsmblk_shard_rotation_carry(lsmblk_ctx* ctx, const uint64_t* carry_in, uint6
  * nseg + 1 entry indices of ext) and their blocks, packed, into out / blk_off as lsmblk_encode_batch
  * writes them; seg_blk (u32[seg_cap]) receives every segment's first block.  stats (u64[8]): [0]
  * blocks [1] bytes [2] segments [3] error flags [4] first segment continues [5] last segment
- * continues [6] first entry [7] end entry.  Asynchronous. */
+ * continues [6] first entry (carry_in.p) [7] end entry (n_own + carry_out.p; a range wholly inside an
+ * earlier rank's block, carry_in.p >= n_own, has no segments and reports the empty span [p, p)).
+ * Asynchronous. */
 int lsmblk_shard_encode_batch(lsmblk_ctx* ctx, const lsmblk_kv_stream* ext, uint8_t* out, uint64_t out_cap,
                               uint64_t* blk_off, uint64_t blk_cap, uint32_t* seg_start, uint32_t* seg_blk,
                               uint32_t seg_cap, uint64_t* stats, void* stream);

@@ -1839,6 +1839,9 @@ __global__ void shard_carry_kernel(RotArgs a, const uint64_t* cin, uint64_t* cou
     segs = cnt + 1;
     if (fl == m) {  // the last SST ends where the next range starts (or the stream ends)
       end = m;
+      // no halo at all: F is n both for an SST that ends at n and for a lifting that ran off the
+      // end, so without LAST nothing tells whether the open SST reached its target
+      if (m >= n && !a.shard_last) err |= LSMBLK_ERR_SEGMENTS;
     } else {        // it continues: its block chain crosses m
       const uint64_t pos = lift_before(a, x, accx, m, top, err);
       const u32x2 v = a.JS[pos];
@@ -1903,7 +1906,8 @@ __global__ void shard_stats_kernel(uint64_t* stats, const uint64_t* est, const u
   stats[4] = segs && w[kShD0] > 0;
   stats[5] = segs && w[kShDout] > 0;
   stats[6] = w[kShP];
-  stats[7] = w[kShEnd];
+  // (a range swallowed by an earlier range's crossing block, p >= m: the empty span [p, p))
+  stats[7] = w[kShEnd] > w[kShP] ? w[kShEnd] : w[kShP];
 }
 
 // Level k: chain elements [2^k, 2^(k+1)) from [0, 2^k) through F^(2^k) (= cur), then
