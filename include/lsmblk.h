@@ -680,12 +680,14 @@ int lsmblk_sst_get_batch(lsmblk_ctx* ctx, const uint8_t* files, const uint64_t* 
                          uint32_t* val_off, uint64_t* stats, void* stream);
 
 /* ------------------------------------------------------------------ LSM point reads (device) */
-/* LsmStorageInner::get_with_ts (src/lsm_storage.rs:361-439) below the memtables, for a batch of keys
- * over an LSM view of the opened set: every L0 table in order, per level the one table whose key
- * range holds the key, keep_table (key_within, then the bloom test) on each, the merge, the reader's
- * view at read_ts, `key == query && !value.is_empty()`.  The memtables stay on the host.
+/* LsmStorageInner::get_with_ts (src/lsm_storage.rs:361-439) for a batch of keys over an LSM view of
+ * the opened set: the view's memtable runs (none, nmem == 0: the read below the memtables), every L0
+ * table in order, per level the one table whose key range holds the key, keep_table (key_within, then
+ * the bloom test) on each table, the merge, the reader's view at read_ts,
+ * `key == query && !value.is_empty()`.
  *
- * Sources, in priority order: source i < nl0 is table l0[i] (l0_sstables order = MergeIterator::
+ * Sources, in priority order (the ordinals below are the tables' with nmem == 0; the memtable runs go
+ * first and shift them by nmem, see lsmblk_lsm_view): source i < nl0 is table l0[i] (l0_sstables order = MergeIterator::
  * create's index order); source nl0 + l is level l, whose tables are in key order and do not overlap
  * (SstConcatIterator::check_sst_valid, src/iterators/concat_iterator.rs:82-93).  A level's source
  * for a key is the last table of the level with first_key <= key, which must then pass
@@ -710,7 +712,52 @@ typedef struct {            /* all device pointers */
   uint32_t nlevel;
   const uint32_t* level_sst;    /* u32[level_start[nlevel]]: per level its SST ids in key order */
   const uint32_t* level_start;  /* u32[nlevel+1], [0] = 0, non-decreasing; an empty level is allowed */
-} lsmblk_lsm_view;
+  const lsmblk_kv_stream* mem;  /* host struct of device arrays: all memtable runs back to back; mem->n = their entries */
+  const uint32_t* mem_start;    /* device u32[nmem+1], the run_start shape: run r = entries [mem_start[r], mem_start[r+1]) */
+  uint32_t nmem;                /* 0 .. 64; 0: the view as it was */
+} lsmblk_lsm_view;              /* 56 bytes (32 before the memtable runs were appended: LSMBLK_ABI_VERSION is
+                                   unchanged, a caller built against the shorter struct must be rebuilt) */
+
+/* The memtable runs of a view (LsmStorageState: memtable, imm_memtables, l0_sstables, levels): the
+ * sources get_with_ts / scan_with_ts consult first (src/lsm_storage.rs:369-380, :460-471), as sorted
+ * SoA streams in device memory -- what lsmblk_memtable_flush yields, uploaded.
+ *   Order      run 0 is the mutable memtable, runs 1 .. the immutable memtables, newest first
+ *              (MergeIterator::create's index order, :369-380).
+ *   Ordinals   mem run r is source r, L0 table i is source nmem + i, level l is source nmem + nl0 + l.
+ *   A run      entries in (key ascending bytewise with a shorter key less, ts descending) order, keys of
+ *              1 .. 65535 bytes, values of at most 65535 bytes.  lsmblk_memtable_flush yields such runs
+ *              with one entry per key; several versions per key are allowed.  This is NOT checked: for
+ *              other runs the result is unspecified, every search and walk bounded by the run's entry count.
+ *   Landing    in every mode (flags 0, MVCC, NEWEST) the first entry of the run whose key is >= the query
+ *              or the bound: SkipMap::range has no binary-search quirk.  No key-range test, no bloom filter.
+ *   Point read, decider rule (flags 0 / LSMBLK_GET_MVCC): the mem runs are consulted first, in order; a
+ *              run whose landing is on the key is the decider: its versions are walked forward while
+ *              ts > read_ts -> FOUND / TOMBSTONE / ABSENT, and no later source is consulted, even when
+ *              the run holds no visible version and a table does.
+ *   Point read, LSMBLK_LSM_GET_NEWEST: every mem run and every passing table is searched; the largest
+ *              ts <= read_ts wins, the lower ordinal on an equal ts (a memtable beats a table).
+ *   A mem hit  src = r, sst = hit_blk = 0xFFFFFFFF, hit_ent = the entry's index in mem, val_pos =
+ *              mem->val_off[hit_ent] (an offset into mem->vals, not into files).  seeks counts every source
+ *              searched, mem runs included: every mem run up to the decider (all of them when no mem run
+ *              decides; NEWEST: all).  bloom_out counts tables only.  The value gather copies mem hits
+ *              from mem->vals and table hits from files into one vals / val_off in query order; stats[1]
+ *              and stats[2] count both kinds.
+ *   Range scan a mem run is a source of range q iff it is not empty and passes range_overlap on its
+ *              first and last key (the rule a table passes).  Mem sources come before the L0 tables and
+ *              count in res[q].sources, in stats[7] and against sub_cap.  The run's slice: begin = the
+ *              run's start (Unbounded), the first entry with key >= k (Included(k)) or with key > k,
+ *              after all of k's versions (Excluded(k)); end = the first entry at or after begin with
+ *              key > upper (Included) or >= upper (Excluded), the run's end for an unbounded upper.  The
+ *              slices are copied into raw with the bytes they have in mem, ordered by range and then by
+ *              source; the merge, the reader's view, NEWEST, the capacity contract, seg_start and every
+ *              stats word are the ones described below, over those runs.
+ *   View check (device, same call, before anything runs): SEGMENTS when mem_start[0] != 0, mem_start
+ *              decreases or mem_start[nmem] != mem->n, reported as a bad level_start is: no lookup or
+ *              scan runs.
+ *   Host       nmem > 64, or nmem > 0 with mem == NULL, mem_start == NULL or a NULL array in mem
+ *              (keys, key_off, vals, val_off, ts): LSMBLK_E_INVAL.
+ *   No SST     with nmem > 0 and a view that names no table (nl0 == 0, nlevel == 0), nsst == 0 with NULL
+ *              files / file_off / desc / index is valid.  With nmem == 0 every rule is what it was. */
 
 /* Result of one key (48 bytes). */
 typedef struct {
@@ -833,9 +880,11 @@ int lsmblk_read_filter_batch(lsmblk_ctx* ctx, const lsmblk_kv_stream* in, const 
                              uint32_t* out_seg_start, uint64_t* stats, void* stream);
 
 /* ------------------------------------------------------------------ LSM range scans (device) */
-/* LsmStorageInner::scan_with_ts (src/lsm_storage.rs:446-550) below the memtables, for a batch of
- * ranges over an LSM view of the opened set (the lsmblk_lsm_view of lsmblk_lsm_get_batch, checked on
- * the device by the same check before anything else runs).  The memtable iterators stay on the host.
+/* LsmStorageInner::scan_with_ts (src/lsm_storage.rs:446-550) for a batch of ranges over an LSM view
+ * of the opened set (the lsmblk_lsm_view of lsmblk_lsm_get_batch, checked on the device by the same
+ * check before anything else runs).  The view's memtable runs are the first sources of every range
+ * (lsmblk_lsm_view: their slices, their place in raw); with nmem == 0 this is the scan below the
+ * memtables.
  *
  * Sources of a range, in priority order (MergeIterator::create's index order): every L0 table, in l0
  * order, that passes range_overlap(lower, upper, first_key, last_key) (:142-167, :474-502), then

@@ -100,8 +100,9 @@ class GetResultC(ctypes.Structure):
 
 
 class LsmViewC(ctypes.Structure):
-    """lsmblk_lsm_view (a host struct of device pointers)."""
-    _fields_ = [("l0", P), ("nl0", U32), ("nlevel", U32), ("level_sst", P), ("level_start", P)]
+    """lsmblk_lsm_view (56 bytes: a host struct of device pointers; mem points at a host lsmblk_kv_stream)."""
+    _fields_ = [("l0", P), ("nl0", U32), ("nlevel", U32), ("level_sst", P), ("level_start", P),
+                ("mem", ctypes.POINTER(KVStreamC)), ("mem_start", P), ("nmem", U32)]
 
 
 class LsmGetResultC(ctypes.Structure):

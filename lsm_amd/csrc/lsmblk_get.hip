@@ -17,9 +17,10 @@
 //                           the version walk
 //     val_scan_kernel       value sizes of the FOUND lookups -> val_off (one workgroup)
 //     val_gather_kernel     one wave per FOUND lookup copies its value
-//   lsmblk_lsm_get_batch    get_with_ts below the memtables (lsm_storage.rs:381-438) for a batch of keys
-//                           over an LSM view of the opened set: L0 tables, levels, one answer per key
-//     lsm_view_check_kernel one lane per view entry: ids, failed opens, level_start, check_sst_valid
+//   lsmblk_lsm_get_batch    get_with_ts (lsm_storage.rs:361-438) for a batch of keys over an LSM view of
+//                           the opened set: memtable runs, L0 tables, levels, one answer per key
+//     lsm_view_check_kernel one lane per view entry: ids, failed opens, level_start, check_sst_valid;
+//                           mem_start
 //     lsm_get_kernel        one wave per key: lane s holds source s's table (a level's by a search over
 //                           its tables' first-key images), every lane runs keep_table for its own,
 //                           the passing sources are read in priority order by sst_lookup -- the
@@ -29,8 +30,8 @@
 //                           tested on every entry, the landing included -- LsmIterator::new's untested
 //                           first position (lsm_iterator.rs:29-43) belongs to the merged iterator and
 //                           is not reproduced per SST.  Kernels: see "scan" below
-//   lsmblk_lsm_scan_batch   scan_with_ts below the memtables (lsm_storage.rs:446-550) for a batch of ranges
-//                           over an LSM view: every passing table scanned by the scan kernels, a
+//   lsmblk_lsm_scan_batch   scan_with_ts (lsm_storage.rs:446-550) for a batch of ranges over an LSM view:
+//                           every passing memtable run sliced, every passing table scanned by the scan kernels, a
 //                           segmented merge per range, the reader's view.  Kernels: see "the LSM range
 //                           scan" below
 #include "lsmblk_dev.hpp"
@@ -268,12 +269,26 @@ struct OpenedSet {  // what lsmblk_sst_open_batch made of the resident files
   const lsmblk_sst_desc* desc;
   const lsmblk_sst_index* index;
 };
+struct MemArgs {  // the memtable runs of a lsmblk_lsm_view: run r = entries [start[r], start[r + 1]) of the stream
+  const uint8_t* keys;
+  const uint32_t* key_off;
+  const uint8_t* vals;
+  const uint32_t* val_off;
+  const uint64_t* ts;
+  uint64_t n;
+  const uint32_t* start;
+  uint32_t nmem;       // <= kMaxMem: a run per lane
+  uint32_t key_bytes;  // key_off[n], read by the kernels that compare keys (mem_keys): the arena's end
+};
 struct ViewArgs {  // lsmblk_lsm_view
   const uint32_t* l0;
   uint32_t nl0, nlevel;
   const uint32_t* level_sst;
   const uint32_t* level_start;
+  MemArgs mem;
 };
+constexpr uint32_t kMaxMem = 64;
+static_assert(sizeof(lsmblk_lsm_view) == 56, "lsmblk_lsm_view: the memtable runs are its last three fields");
 struct PointArgs {  // a batch of point reads and where their values go
   const uint8_t* qkeys;
   const uint32_t* qkey_off;
@@ -756,13 +771,18 @@ __device__ int lane_cmp2(const uint8_t* x, uint32_t la, const uint8_t* y, uint32
 }
 
 // The view against the opened set, one lane per view entry (the L0 ids, then the level ids):
-// level_start first, by every workgroup -- it bounds the reads of level_sst -- then per entry the id,
+// level_start (and mem_start, which bounds every read of a memtable run, against mem->n) first, by
+// every workgroup -- it bounds the reads of level_sst -- then per entry the id,
 // its open, and for a level entry with a right neighbour check_sst_valid's order
 // (concat_iterator.rs:82-93), last_key(i) < first_key(i + 1), through the descriptors' key positions.
 __global__ __launch_bounds__(256) void lsm_view_check_kernel(ViewCheckArgs a) {
   int sb = 0;
   for (uint32_t i = threadIdx.x; i < a.nlevel; i += 256)
     sb |= (i == 0 && a.level_start[0] != 0) || a.level_start[i + 1] < a.level_start[i];
+  // mem_start, the same shape over the memtable runs' entries: it bounds every read of a run
+  if (const uint32_t i = threadIdx.x; i < a.mem.nmem)
+    sb |= (i == 0 && a.mem.start[0] != 0) || a.mem.start[i + 1] < a.mem.start[i] ||
+          (i + 1 == a.mem.nmem && a.mem.start[i + 1] != a.mem.n);
   uint32_t err = 0;
   if (__syncthreads_or(sb)) {
     if (blockIdx.x == 0 && threadIdx.x == 0) err = LSMBLK_ERR_SEGMENTS;
@@ -870,7 +890,111 @@ __device__ __forceinline__ bool lane_may_contain(const OpenedSet& o, uint32_t t,
   return !miss;
 }
 
+// The runs with key_bytes filled in (wave-uniform; only after the view check passed: n is mem_start's end).
+__device__ __forceinline__ MemArgs mem_keys(MemArgs m) {
+  m.key_bytes = uni(m.key_off[m.n]);
+  return m;
+}
+
+// Entry i of the memtable runs' stream against the query by one lane, images first as lane_cmp_img:
+// the key's leading 16 bytes come from ONE 16-byte load at any alignment wherever 16 bytes from the
+// key's start lie inside the arena (every key but the last few) -- a probe is then three loads, not
+// eighteen -- and the bytes past the key's end are masked off.
+__device__ __forceinline__ int mem_cmp(const MemArgs& m, uint32_t i, const QKey& q, uint64_t qhi, uint64_t qlo) {
+  const uint32_t k0 = m.key_off[i], len = m.key_off[i + 1] - k0;
+  const uint8_t* p = m.keys + k0;
+  if (uint64_t(k0) + 16 > m.key_bytes) return lane_cmp_img(p, len, q, qhi, qlo);
+  const u32x4 v = *reinterpret_cast<const u32x4*>(p);
+  uint64_t hi = (uint64_t(__builtin_bswap32(v.x)) << 32) | __builtin_bswap32(v.y);
+  uint64_t lo = (uint64_t(__builtin_bswap32(v.z)) << 32) | __builtin_bswap32(v.w);
+  if (len < 16) {  // (len >= 1 for a run that obeys the precondition; 0 keeps nothing)
+    hi = len >= 8 ? hi : (len ? hi & (~0ull << (8 * (8 - len))) : 0ull);
+    lo = len > 8 ? lo & (~0ull << (8 * (16 - len))) : 0ull;
+  }
+  if (hi != qhi) return hi < qhi ? -1 : 1;
+  if (lo != qlo) return lo < qlo ? -1 : 1;
+  return lane_cmp(p, len, q);
+}
+
+// The wave's lanes over the memtable runs: the 64 lanes are split evenly into lane groups of g = 2^lg
+// lanes, the largest power of two with nmem g <= 64, and run r is searched by lanes [r g, (r + 1) g):
+// one run has the whole wave, four runs 16 lanes each, more than 32 runs a lane each.
+struct MemGroups {
+  uint32_t lg, run, sub;  // log2 g; the lane's run and its place in the group
+  bool on;                // the lane's group has a run
+  __device__ __forceinline__ uint32_t g() const { return 1u << lg; }
+  __device__ __forceinline__ bool lead() const { return on && sub == 0; }
+  // the ballot bits of the lane's own group, counted
+  __device__ __forceinline__ uint32_t count(uint64_t ballot) const {
+    const uint64_t m = lg == 6 ? ~0ull : (1ull << g()) - 1;
+    return uint32_t(__builtin_popcountll((ballot >> (run << lg)) & m));
+  }
+};
+__device__ __forceinline__ MemGroups mem_groups(uint32_t nmem) {
+  const uint32_t lg = nmem > 1 ? uint32_t(__builtin_clz(nmem - 1)) - 26u : 6u;  // 6 - ceil(log2 nmem)
+  const uint32_t l = lane_id();
+  return MemGroups{lg, l >> lg, l & ((1u << lg) - 1), (l >> lg) < nmem};
+}
+
+// First index of [lo, hi) where pred turns false (hi: nowhere), pred true on a prefix of the range, by
+// the lane's group for the group's own range (lo, hi and `on` are the same in every lane of a group;
+// every lane of the wave calls this): kary_first_false's step with g probes, so a step cuts the range
+// (g + 1)-fold -- g = 1: in halves -- for one round trip, the groups' round trips in flight together.
+// Every step shrinks every live range, so the steps are bounded by the longest range.
+template <class Pred>
+__device__ __forceinline__ uint32_t group_first_false(const MemGroups& G, uint32_t lo, uint32_t hi, bool on, Pred pred) {
+  const uint32_t sh = G.lg ? G.lg : 1u;
+  while (__ballot(on && lo < hi)) {
+    const uint32_t n = on && lo < hi ? hi - lo : 0u;
+    const uint32_t stride = (n + (1u << sh) - 1) >> sh;
+    const uint32_t idx = lo + (G.sub + 1) * stride - 1;  // (n <= g: stride 1, a probe per entry)
+    const bool p = n && idx < hi && pred(idx);
+    const uint32_t cnt = G.count(__ballot(p));
+    const uint32_t nhi = lo + (cnt + 1) * stride - 1;  // the first false probe (all true: the range's end)
+    if (n) {
+      lo += cnt * stride;
+      if (cnt < G.g() && nhi < hi) hi = nhi;
+    }
+  }
+  return lo;
+}
+
+// A run's read of one key by its lane group: the landing is the first entry with key >= the query
+// (SkipMap::range: the same in every mode); on the key, the group's first lane walks its versions
+// forward while ts > read_ts.  Both loops are bounded by the run's entries.  The result is in the
+// group's first lane.
+struct MemLook {
+  bool on_key;   // the landing entry's key is the query
+  uint32_t hit;  // the visible version's index in the stream; kNone: none
+  uint32_t vlen;
+  uint64_t ts;
+};
+__device__ __forceinline__ MemLook mem_lookup(const MemArgs& m, const MemGroups& G, const QKey& q, uint64_t qhi, uint64_t qlo,
+                                              uint64_t read_ts) {
+  MemLook o{false, kNone, 0, 0};
+  const uint32_t lo = G.on ? m.start[G.run] : 0u, end = G.on ? m.start[G.run + 1] : 0u;
+  const uint32_t land = group_first_false(G, lo, end, G.on, [&](uint32_t i) { return mem_cmp(m, i, q, qhi, qlo) < 0; });
+  if (G.lead()) {
+    for (uint32_t e = land; e < end && mem_cmp(m, e, q, qhi, qlo) == 0; ++e) {
+      o.on_key = true;
+      const uint64_t t = m.ts[e];
+      if (t <= read_ts) {
+        o.hit = e;
+        o.ts = t;
+        o.vlen = m.val_off[e + 1] - m.val_off[e];
+        break;
+      }
+    }
+  }
+  return o;
+}
+
 // One wave per key, grid-strided, over the sources in priority order, 64 at a time:
+//   memtable runs  (a view with any) before every table: the lanes are split into a group per run
+//            (mem_groups), every group searches its own run, so all runs' round trips are in flight
+//            together; the landings are folded in ordinal order -- the first run on the key decides
+//            and no table is touched, or (NEWEST) the newest visible version of any run is the answer
+//            the tables have to beat.  Tables are sources nmem + ...
 //   tables   lane s holds source s's table: an L0 id, or the level's table routed by the wave -- a
 //            view of up to 64 level tables in all has every table's image probed by its own lane
 //            at once and each level's bounds counted out of the two ballots; a larger one runs
@@ -883,6 +1007,9 @@ __device__ __forceinline__ bool lane_may_contain(const OpenedSet& o, uint32_t t,
 // Decider rule: the reads end at the first source whose landing is on the key (or whose path is
 // malformed); bloom_out counts the rejected sources before it.  NEWEST: every passing source is
 // read, the best (ts, lower ordinal) kept.
+// kMem: the view has memtable runs.  A view without any runs the <false> form, which holds nothing
+// of the runs: what it cost callers without memtables was measured ("Memtable runs ...").
+template <bool kMem>
 __global__ __launch_bounds__(64 * kGetWaves) __attribute__((amdgpu_waves_per_eu(8))) void lsm_get_kernel(LsmGetArgs a) {
   __shared__ __attribute__((aligned(16))) uint8_t img[kGetWaves][kGetImg];
   const uint32_t l = lane_id();
@@ -893,6 +1020,7 @@ __global__ __launch_bounds__(64 * kGetWaves) __attribute__((amdgpu_waves_per_eu(
   const OpenedSet& o = a;
   const bool run = uni(*a.vflag) == 0;
   const uint32_t nsrc = a.nl0 + a.nlevel;
+  const uint32_t nmem = kMem ? a.mem.nmem : 0u;  // the tables' first ordinal
   const uint32_t nlv = run && a.nlevel ? uni(a.level_start[a.nlevel]) : 0u;  // level tables in all
   uint32_t err = 0, nfound = 0;
   if (blockIdx.x == 0 && threadIdx.x == 0) a.stats[0] = a.nq;
@@ -916,6 +1044,43 @@ __global__ __launch_bounds__(64 * kGetWaves) __attribute__((amdgpu_waves_per_eu(
         lem = __ballot((c & 2) != 0);
       }
       bool decided = false;
+      if constexpr (kMem) {
+        const MemArgs mem = mem_keys(a.mem);
+        const MemGroups G = mem_groups(mem.nmem);
+        const MemLook ml = mem_lookup(mem, G, q, qhi, qlo, read_ts);
+        // (a run's result is in its group's first lane: lane order is ordinal order)
+        const uint64_t onm = __ballot(ml.on_key), hitm = __ballot(ml.hit != kNone);
+        uint32_t w = kNone;  // the lane that answers
+        seeks = nmem;
+        if (!newest) {
+          if (onm) {  // the decider: the runs after it count as never consulted
+            w = uint32_t(__builtin_ctzll(onm));
+            seeks = (w >> G.lg) + 1;
+            decided = true;
+          }
+        } else {
+          uint64_t best = 0;
+          for (uint64_t m = hitm; m; m &= m - 1) {  // ordinal order: an equal ts keeps the lower run
+            const uint32_t j = uint32_t(__builtin_ctzll(m));
+            const uint64_t t = lane64(ml.ts, j);
+            if (w == kNone || t > best) {
+              w = j;
+              best = t;
+            }
+          }
+        }
+        if (w != kNone) {
+          asrc = w >> G.lg;  // (sst and hit_blk stay 0xFFFFFFFF: no table)
+          ans.landed = ans.on_key = true;
+          if ((hitm >> w) & 1) {
+            ans.hit_ent = uint32_t(__builtin_amdgcn_readlane(ml.hit, w));
+            ans.vlen = uint32_t(__builtin_amdgcn_readlane(ml.vlen, w));
+            ans.ts = lane64(ml.ts, w);
+            ans.val_pos = uni(a.mem.val_off[ans.hit_ent]);
+            ans.status = ans.vlen ? LSMBLK_GET_FOUND : LSMBLK_GET_TOMBSTONE;
+          }
+        }
+      }
       for (uint32_t base = 0; base < nsrc && !decided; base += 64) {
         const uint32_t cnt = nsrc - base < 64 ? nsrc - base : 64;
         uint32_t myt = kNone;  // lane s: the table of source base + s
@@ -958,7 +1123,7 @@ __global__ __launch_bounds__(64 * kGetWaves) __attribute__((amdgpu_waves_per_eu(
           if (!newest) {
             if (k.on_key || bad) {
               ans = k;
-              asrc = base + s;
+              asrc = nmem + base + s;
               asst = t;
               decided = true;
               consulted = (2ull << s) - 1;  // the sources up to the decider
@@ -966,7 +1131,7 @@ __global__ __launch_bounds__(64 * kGetWaves) __attribute__((amdgpu_waves_per_eu(
             }
           } else if (k.status != LSMBLK_GET_ABSENT && (asrc == kNone || k.ts > ans.ts)) {
             ans = k;
-            asrc = base + s;
+            asrc = nmem + base + s;
             asst = t;
           }
         }
@@ -1019,6 +1184,13 @@ __global__ __launch_bounds__(1024) void val_scan_kernel(Args a) {
   }
 }
 
+// The arena a FOUND lookup's val_pos points into: the files, or for a hit in a memtable run of the
+// view (src < nmem) the runs' value arena.
+__device__ __forceinline__ const uint8_t* value_arena(const GetArgs& a, uint64_t) { return a.files; }
+__device__ __forceinline__ const uint8_t* value_arena(const LsmGetArgs& a, uint64_t q) {
+  return uni(a.res[q].src) < a.mem.nmem ? a.mem.vals : a.files;
+}
+
 // One wave per lookup, grid-strided: a FOUND lookup's value bytes into its place.
 template <class Args>
 __global__ __launch_bounds__(256) void val_gather_kernel(Args a) {
@@ -1028,7 +1200,7 @@ __global__ __launch_bounds__(256) void val_gather_kernel(Args a) {
     if (uni(a.res[q].status) != LSMBLK_GET_FOUND) continue;
     const uint32_t vl = uni(a.res[q].vlen), o = uni(a.val_off[q]);
     if (uint64_t(o) + vl > a.val_cap) continue;
-    wave_copy_bytes(a.vals + o, a.files + uni64(a.res[q].val_pos), vl);
+    wave_copy_bytes(a.vals + o, value_arena(a, q) + uni64(a.res[q].val_pos), vl);
   }
 }
 
@@ -1069,6 +1241,8 @@ struct ScanArgs : OpenedSet, BoundArgs {
   // are per scan
   const uint64_t* nq_dev;
   const uint32_t* parent;
+  // ... and the view's memtable runs: table scan "table" nsst + r is the slice of run r (kSub only)
+  MemArgs mem;
 };
 template <bool kSub>
 __device__ __forceinline__ uint64_t scan_nq(const ScanArgs& a) {
@@ -1130,12 +1304,17 @@ __global__ __launch_bounds__(64 * kGetWaves) void scan_bounds_kernel(ScanArgs a)
   const uint64_t nq = scan_nq<kSub>(a);
   for (uint64_t qi = uint64_t(blockIdx.x) * kGetWaves + wave_id(); qi < nq; qi += stride) {
     uint32_t status = LSMBLK_SCAN_EMPTY, b0 = kNone, e0 = kNone, b1 = kNone, e1 = kNone, nb = 0;
-    bool malformed = false;
+    bool malformed = false, mem = false;
     do {
       uint64_t pq = qi;  // the range whose bounds this scan takes
       if constexpr (kSub) pq = uni(a.parent[qi]);
       const uint32_t s = uni(a.q_sst[qi]), bnd = uni(a.q_bound[pq]);
       const uint32_t lk = bnd & 3, uk = (bnd >> 2) & 3;
+      if constexpr (kSub) {
+        // a memtable run's slice: lsm_scan_expand_kernel searched the run and wrote the result
+        mem = s >= a.nsst && s - a.nsst < a.mem.nmem;
+        if (mem) break;
+      }
       if (s >= a.nsst || lk == 3 || uk == 3) {
         err |= LSMBLK_ERR_SEGMENTS;
         break;
@@ -1266,7 +1445,7 @@ __global__ __launch_bounds__(64 * kGetWaves) void scan_bounds_kernel(ScanArgs a)
       r.ent1 = e1;
       r.blocks = nb;
       r.n = 0;
-      a.res[qi] = r;
+      if (!mem) a.res[qi] = r;
       // (a table scan of the LSM scan marks a malformed search as well: its range takes no partial merge)
       a.qbad[qi] = kSub && malformed ? 1u : 0u;
     }
@@ -1341,6 +1520,18 @@ __global__ __launch_bounds__(64 * kGetWaves) void scan_count_kernel(ScanArgs a) 
   for (uint64_t u = uint64_t(blockIdx.x) * kGetWaves + wave_id(); u < nu; u += stride) {
     const uint32_t q = unit_query(a.ubase, nq, uint32_t(u));
     uint64_t ne = 0, kb = 0, vb = 0;
+    if constexpr (kSub) {
+      if (uni(a.q_sst[q]) >= a.nsst) {  // a memtable run's slice: one unit, its sizes are offset differences
+        const uint32_t b = uni(a.res[q].blk0), e = uni(a.res[q].blk1);
+        if (l == 0) {
+          const bool in = b <= e && e <= a.mem.n;
+          a.ucnt[3 * u] = in ? e - b : 0u;
+          a.ucnt[3 * u + 1] = in ? a.mem.key_off[e] - a.mem.key_off[b] : 0u;
+          a.ucnt[3 * u + 2] = in ? a.mem.val_off[e] - a.mem.val_off[b] : 0u;
+        }
+        continue;
+      }
+    }
     const bool ok = unit_blocks(a, q, uint32_t(u), S, [&](const auto& im, const BlockHdr& h, uint32_t w0, uint32_t w1) {
       bool bad = false;
       for (uint32_t c = 0; c < h.n; c += 64) {  // every entry is checked, the window's are counted
@@ -1468,6 +1659,26 @@ __device__ __forceinline__ void quarter_copy(uint8_t* dst, const Img& im, uint32
   if (x < len) dst[x] = uint8_t(im.u8(src + x));
 }
 
+// Entries [b, e) of the memtable runs' stream -> out from entry ei, key byte ko, value byte vo, by the
+// whole wave: the offsets rebased and the ts entry by entry, the key and the value bytes each as one
+// contiguous copy at any alignment.
+__device__ __forceinline__ void mem_emit(const MemArgs& m, const DevStream& out, uint32_t b, uint32_t e, uint64_t ei,
+                                         uint64_t ko, uint64_t vo) {
+  if (b >= e || e > m.n) return;
+  const uint32_t k0 = uni(m.key_off[b]), v0 = uni(m.val_off[b]);
+  const uint32_t kb = uni(m.key_off[e]) - k0, vb = uni(m.val_off[e]) - v0;
+  // (the totals passed the capacity check; a slice past a capacity would be a stream that changed
+  // since the count: it is not written)
+  if (ei + (e - b) > out.entry_cap || ko + kb > out.key_cap || vo + vb > out.val_cap) return;
+  for (uint32_t i = lane_id(); i < e - b; i += 64) {
+    out.key_off[ei + i] = uint32_t(ko) + (m.key_off[b + i] - k0);
+    out.val_off[ei + i] = uint32_t(vo) + (m.val_off[b + i] - v0);
+    out.ts[ei + i] = m.ts[b + i];
+  }
+  wave_copy_bytes(out.keys + ko, m.keys + k0, kb);
+  wave_copy_bytes(out.vals + vo, m.vals + v0, vb);
+}
+
 template <bool kSub>
 __global__ __launch_bounds__(64 * kGetWaves) void scan_emit_kernel(ScanArgs a) {
   __shared__ __attribute__((aligned(16))) uint8_t img[kGetWaves][kGetImg];
@@ -1479,6 +1690,12 @@ __global__ __launch_bounds__(64 * kGetWaves) void scan_emit_kernel(ScanArgs a) {
     const uint32_t q = unit_query(a.ubase, nq, uint32_t(u));
     if (uni(a.qbad[q])) continue;
     uint64_t ei = uni64(a.ucnt[3 * u]), ko = uni64(a.ucnt[3 * u + 1]), vo = uni64(a.ucnt[3 * u + 2]);
+    if constexpr (kSub) {
+      if (uni(a.q_sst[q]) >= a.nsst) {
+        mem_emit(a.mem, a.out, uni(a.res[q].blk0), uni(a.res[q].blk1), ei, ko, vo);
+        continue;
+      }
+    }
     (void)unit_blocks(a, q, uint32_t(u), S, [&](const auto& im, const BlockHdr& h, uint32_t w0, uint32_t w1) {
       for (uint32_t c = w0; c < w1; c += 64) {
         const uint32_t e = c + l, cnt = w1 - c < 64 ? w1 - c : 64u;
@@ -1535,16 +1752,19 @@ void launch_scan(const ScanArgs& a, uint32_t qgrid, uint32_t ugrid, bool emit, h
 }
 
 // ---------------------------------------------------------------- the LSM range scan
-// lsmblk_lsm_scan_batch: scan_with_ts below the memtables for a batch of ranges over an LSM view.
+// lsmblk_lsm_scan_batch: scan_with_ts for a batch of ranges over an LSM view.
 //   lsm_view_check_kernel     the point read's, unchanged
 //   lsm_scan_expand_kernel    <false> one wave per range: the tables that pass range_overlap, counted
 //                             (L0: every table by its own lane; a level: the span between two k-ary
-//                             searches, then every table of the span by its own lane)
+//                             searches, then every table of the span by its own lane).  <.., true>, a
+//                             view with memtable runs: the runs first, each by its lane group, and the
+//                             fill pass finds a passing run's slice and writes its scan's result
 //   lsm_scan_subs_kernel      one workgroup: sbase = exclusive scan of the counts, the total against
 //                             sub_cap -> nsub, the table scans that run (0: refused view, sub_cap short)
 //   lsm_scan_expand_kernel    <true> the same walk, writing (range, table) of every table scan
 //   lsm_scan_sub_*_kernel     the five scan kernels over the table scans -> the raw stream, run after
-//                             run, and sseg = every run's first raw entry
+//                             run, and sseg = every run's first raw entry (a memtable run's slice: its
+//                             bounds are skipped, its sizes are offset differences, its emit one copy)
 //   lsm_scan_rank_kernel      the segmented merge: one raw entry per lane, its merge rank among the
 //                             runs of its range by a search in every other run -> slot (<true>,
 //                             LSMBLK_LSM_SCAN_NEWEST: the rank by (key, ts descending), no ownership)
@@ -1568,7 +1788,8 @@ struct LsmScanArgs : OpenedSet, ViewArgs, BoundArgs {
   uint32_t* pbad;         // nq: a block on the range's path is malformed
   uint32_t* mcnt;         // nq: merged entries
   uint32_t* sub_q;        // sub_cap: the table scan's range ...
-  uint32_t* sub_sst;      // ... and table
+  uint32_t* sub_sst;      // ... and table (nsst + r: memtable run r)
+  lsmblk_scan_result* sres;  // sub_cap: the table scans' results (a memtable run's slice is written by the expansion)
   uint32_t* sseg;         // sub_cap + 1: first raw entry of every run
   const uint32_t* sbad;   // sub_cap: the table scans' qbad
   uint32_t* slot;         // slot_cap: merged position -> raw entry + 1 (0: not kept)
@@ -1599,7 +1820,7 @@ __device__ __forceinline__ int lane_cmp_img2(const uint8_t* x, uint32_t lx, cons
 // lies within the upper bound are one too: a level of more than 64 tables is cut to that span by two
 // k-ary searches first.  kFill false: scnt[q] = the passing tables; true: their (range, table) pairs
 // from sbase[q] on.
-template <bool kFill>
+template <bool kFill, bool kMem>
 __global__ __launch_bounds__(64 * kGetWaves) void lsm_scan_expand_kernel(LsmScanArgs a) {
   const uint32_t l = lane_id();
   if constexpr (kFill) {
@@ -1668,6 +1889,54 @@ __global__ __launch_bounds__(64 * kGetWaves) void lsm_scan_expand_kernel(LsmScan
           cnt += uint32_t(__builtin_popcountll(m));
         }
       };
+      // the memtable runs first, each by its own lane group (mem_groups): a run that is not empty passes
+      // as a table does, on its first and last key; its table scan is "table" nsst + r
+      if constexpr (kMem) {
+        const MemArgs mem = mem_keys(a.mem);
+        const MemGroups G = mem_groups(mem.nmem);
+        bool ok = false;
+        uint32_t x0 = 0, x1 = 0;
+        if (G.on) {
+          x0 = a.mem.start[G.run];
+          x1 = a.mem.start[G.run + 1];
+          ok = x1 > x0;
+          if (ok && uk) {
+            const int c = mem_cmp(mem, x0, up, uhi, ulo);
+            ok = uk == LSMBLK_BOUND_EXCLUDED ? c < 0 : c <= 0;
+          }
+          if (ok && lk) {
+            const int c = mem_cmp(mem, x1 - 1, lo, lhi, llo);
+            ok = !(lk == LSMBLK_BOUND_EXCLUDED ? c <= 0 : c < 0);
+          }
+        }
+        const uint64_t m = __ballot(ok && G.sub == 0);  // a bit per passing run, in ordinal order
+        if constexpr (kFill) {
+          // The slice, as (blk0 = begin, blk1 = end) entry indices of the runs' stream in one "block":
+          // two searches over the run by its lane group, the same in every mode.  begin: the first key
+          // >= lower (Excluded: > lower, after all its versions); end: the first key at or after begin
+          // > upper (Excluded: >= upper).
+          const uint64_t x = uint64_t(base) + uint32_t(__builtin_popcountll(m & ((1ull << (G.run << G.lg)) - 1)));
+          const bool on = ok && x < a.sub_cap;
+          const bool excl = lk == LSMBLK_BOUND_EXCLUDED, strict = uk == LSMBLK_BOUND_EXCLUDED;
+          uint32_t b = x0, e = x1;
+          if (lk)
+            b = group_first_false(G, x0, x1, on, [&](uint32_t i) {
+              const int c = mem_cmp(mem, i, lo, lhi, llo);
+              return excl ? c <= 0 : c < 0;
+            });
+          if (uk)
+            e = group_first_false(G, b, x1, on, [&](uint32_t i) {
+              const int c = mem_cmp(mem, i, up, uhi, ulo);
+              return strict ? c < 0 : c <= 0;
+            });
+          if (on && G.sub == 0) {
+            a.sub_q[x] = uint32_t(qi);
+            a.sub_sst[x] = a.nsst + G.run;
+            a.sres[x] = lsmblk_scan_result{LSMBLK_SCAN_EMPTY, b, 0, e, 0, e > b ? 1u : 0u, 0};
+          }
+        }
+        cnt += uint32_t(__builtin_popcountll(m));
+      }
       take(a.l0, 0, a.nl0);
       for (uint32_t lv = 0; lv < a.nlevel; ++lv) {
         const uint32_t t0 = uni(a.level_start[lv]), n = uni(a.level_start[lv + 1]) - t0;
@@ -1980,13 +2249,20 @@ bool bad_opened(const OpenedSet& o, bool read) {
          (reinterpret_cast<uintptr_t>(o.index) & 15);
 }
 bool bad_view(const lsmblk_lsm_view* v) {
-  return !v || (v->nl0 && !v->l0) || (v->nlevel && (!v->level_start || !v->level_sst)) ||
-         uint64_t(v->nl0) + v->nlevel >= 0xFFFFFFFFull;
+  if (!v || (v->nl0 && !v->l0) || (v->nlevel && (!v->level_start || !v->level_sst)) ||
+      uint64_t(v->nl0) + v->nlevel + v->nmem >= 0xFFFFFFFFull || v->nmem > kMaxMem)
+    return true;
+  const lsmblk_kv_stream* m = v->mem;
+  return v->nmem && (!m || !v->mem_start || !m->keys || !m->key_off || !m->vals || !m->val_off || !m->ts);
 }
 bool bad_stream(const lsmblk_kv_stream* s) {  // (an absent stream is fine)
   return s && (!s->key_off || !s->val_off || (s->entry_cap && !s->ts) || (s->key_cap && !s->keys) || (s->val_cap && !s->vals));
 }
-ViewArgs view_args(const lsmblk_lsm_view* v) { return ViewArgs{v->l0, v->nl0, v->nlevel, v->level_sst, v->level_start}; }
+ViewArgs view_args(const lsmblk_lsm_view* v) {
+  ViewArgs a{v->l0, v->nl0, v->nlevel, v->level_sst, v->level_start, MemArgs{}};
+  if (v->nmem) a.mem = MemArgs{v->mem->keys, v->mem->key_off, v->mem->vals, v->mem->val_off, v->mem->ts, v->mem->n, v->mem_start, v->nmem, 0};
+  return a;
+}
 
 // The first entry of an offsets array (or of both of a stream's) zeroed: an empty batch's result.
 bool zero_first(uint32_t* off, hipStream_t st) { return !off || hipMemsetAsync(off, 0, 4, st) == hipSuccess; }
@@ -2059,7 +2335,7 @@ LsmScanWs lsm_scan_ws(uint8_t* base, LsmScanArgs& a, ScanArgs& s, uint64_t budge
   a.sub_q = cv.take<uint32_t>(a.sub_cap);
   a.sub_sst = cv.take<uint32_t>(a.sub_cap);
   a.sseg = cv.take<uint32_t>(a.sub_cap + 1);
-  w.sres = cv.take<lsmblk_scan_result>(a.sub_cap);
+  w.sres = a.sres = cv.take<lsmblk_scan_result>(a.sub_cap);
   scan_regions(cv, s, a.sub_cap, budget);
   a.sbad = s.qbad;
   a.slot = cv.take<uint32_t>(a.slot_cap);
@@ -2145,7 +2421,10 @@ int lsmblk_lsm_get_batch(lsmblk_ctx* c, const uint8_t* files, const uint64_t* fi
   const ViewCheckArgs vc{o, v, stats, vflag};
   const GridCap grid(c);
   LSM_LAUNCH(lsm_view_check_kernel, dim3(32), dim3(256), 0, st, vc);
-  LSM_LAUNCH(lsm_get_kernel, dim3(grid(nq, kGetWaves)), dim3(64 * kGetWaves), 0, st, a);
+  if (v.mem.nmem)
+    LSM_LAUNCH_NAMED("lsm_get_kernel", lsm_get_kernel<true>, dim3(grid(nq, kGetWaves)), dim3(64 * kGetWaves), 0, st, a);
+  else
+    LSM_LAUNCH_NAMED("lsm_get_kernel", lsm_get_kernel<false>, dim3(grid(nq, kGetWaves)), dim3(64 * kGetWaves), 0, st, a);
   if (vals) launch_values(a, grid, st);
   return launch_rc();
 }
@@ -2218,14 +2497,24 @@ int lsmblk_lsm_scan_batch(lsmblk_ctx* c, const uint8_t* files, const uint64_t* f
   s.stats = a.sstats;
   s.nq_dev = a.nsub;
   s.parent = a.sub_q;
+  s.mem = v.mem;
 
   const GridCap grid(c);
   LSM_LAUNCH(lsm_view_check_kernel, dim3(32), dim3(256), 0, st, vc);
-  LSM_LAUNCH_NAMED("lsm_scan_expand_count_kernel", lsm_scan_expand_kernel<false>, dim3(grid(nq, kGetWaves)),
-                   dim3(64 * kGetWaves), 0, st, a);
+  // (a view without memtable runs runs the forms that hold nothing of them, under the same names)
+  if (v.mem.nmem)
+    LSM_LAUNCH_NAMED("lsm_scan_expand_count_kernel", (lsm_scan_expand_kernel<false, true>), dim3(grid(nq, kGetWaves)),
+                     dim3(64 * kGetWaves), 0, st, a);
+  else
+    LSM_LAUNCH_NAMED("lsm_scan_expand_count_kernel", (lsm_scan_expand_kernel<false, false>), dim3(grid(nq, kGetWaves)),
+                     dim3(64 * kGetWaves), 0, st, a);
   LSM_LAUNCH(lsm_scan_subs_kernel, dim3(1), dim3(kScanWg), 0, st, a);
-  LSM_LAUNCH_NAMED("lsm_scan_expand_fill_kernel", lsm_scan_expand_kernel<true>, dim3(grid(nq, kGetWaves)),
-                   dim3(64 * kGetWaves), 0, st, a);
+  if (v.mem.nmem)
+    LSM_LAUNCH_NAMED("lsm_scan_expand_fill_kernel", (lsm_scan_expand_kernel<true, true>), dim3(grid(nq, kGetWaves)),
+                     dim3(64 * kGetWaves), 0, st, a);
+  else
+    LSM_LAUNCH_NAMED("lsm_scan_expand_fill_kernel", (lsm_scan_expand_kernel<true, false>), dim3(grid(nq, kGetWaves)),
+                     dim3(64 * kGetWaves), 0, st, a);
   launch_scan<true>(s, grid(sub_cap, kGetWaves), grid(units, kGetWaves), raw != nullptr, st);
   if (raw && newest)
     LSM_LAUNCH_NAMED("lsm_scan_rank_newest_kernel", lsm_scan_rank_kernel<true>, dim3(grid(slot_cap, 256)), dim3(256), 0, st, a);

@@ -1,6 +1,7 @@
 """SST container (SURVEY.md §8 f, rows 3 and 4): whole SST files and the memtable flush source.
 
   MemTable          reference src/mem_table.rs:55-158 (host; the flush source of the encoder)
+  mem_runs          memtables (or KV streams) as the memtable runs of an LsmView: one stream, run_start
   sst_files         SsTableBuilder::build (src/table/builder.rs:68-98) for every SST of an encode
                     or compaction, on the device: framed data section, BlockMeta section,
                     meta_offset, bloom filter over farmhash::fingerprint32, bloom_offset
@@ -14,9 +15,9 @@
                     with the entry and its value (lsmblk_sst_get_batch), and batches of
                     (sst, lower, upper) range scans with every version in range
                     (lsmblk_sst_scan_batch), filtered to a reader's view by batch.read_filter; over an
-                    LsmView (L0 tables and levels of the set) batches of keys with one answer per
-                    key, get_with_ts below the memtables (lsmblk_lsm_get_batch), and batches of
-                    ranges with each range's merged reader's view, scan_with_ts below the memtables
+                    LsmView (memtable runs, L0 tables and levels of the set) batches of keys with one answer per
+                    key, get_with_ts (lsmblk_lsm_get_batch), and batches of
+                    ranges with each range's merged reader's view, scan_with_ts
                     (lsmblk_lsm_scan_batch)
 
 Device work goes through liblsmblk.so; the footer / section parsing here is host logic that mirrors
@@ -237,11 +238,46 @@ def _bound_kind(k):
     return BOUND_KINDS[k] if isinstance(k, str) else int(k)
 
 
+MAX_MEM_RUNS = 64  # lsmblk_lsm_view.nmem
+
+
+def mem_runs(sources, device="cuda"):
+    """The memtable runs of a view: `sources` in priority order -- the mutable memtable, then the
+    immutable ones, newest first -- each a MemTable (through flush_arrays) or a batch.KVStream on the
+    device -> (the runs back to back as one KVStream, run_start: an int32 (u32) tensor of
+    len(sources) + 1).  Run r is entries [run_start[r], run_start[r + 1])."""
+    dev = torch.device(device)
+    # per run (keys, key_off, vals, val_off, ts), the arenas trimmed to the run's bytes
+    parts = [s.flush_arrays() if isinstance(s, MemTable) else s.to_numpy() for s in sources]
+    cat = lambda i, dt: np.concatenate([np.zeros(0, dt)] + [np.asarray(p[i], dt) for p in parts])
+
+    def offsets(i, arena):  # the runs' offsets, each rebased onto its arena's place in the concatenation
+        base, out = 0, [np.zeros(1, np.uint64)]
+        for p in parts:
+            out.append(np.asarray(p[i], np.uint64)[1:] + np.uint64(base))
+            base += len(p[arena])
+        if base > 0xFFFFFFFF:
+            raise ValueError("mem_runs: the runs' bytes do not fit u32 offsets")
+        return np.concatenate(out).astype(np.uint32)
+
+    start = np.concatenate([[0], np.cumsum([len(p[4]) for p in parts])]).astype(np.uint32)
+    kv = batch.KVStream.from_numpy(cat(0, np.uint8), offsets(1, 0), cat(2, np.uint8), offsets(3, 2), cat(4, np.uint64), device=dev)
+    return kv, batch._u32_table(start, dev)
+
+
 class LsmView:
     """An LSM view of an SstSet on the device (lsmblk_lsm_view): `l0` the L0 tables' ids in priority
-    order, `levels` per level its ids in key order.  The tables are checked by every lookup call."""
+    order, `levels` per level its ids in key order, `mem` the memtable runs -- what mem_runs returns,
+    or its `sources` -- which the view keeps alive.  The view is checked by every lookup call."""
 
-    def __init__(self, l0, levels, device):
+    def __init__(self, l0, levels, device, mem=None):
+        if mem is not None and not (isinstance(mem, tuple) and len(mem) == 2 and isinstance(mem[0], batch.KVStream)):
+            mem = mem_runs(mem, device)
+        self.mem, self.mem_start_t = mem if mem is not None else (None, None)
+        self.nmem = self.mem_start_t.numel() - 1 if mem is not None else 0
+        if self.nmem > MAX_MEM_RUNS:
+            raise LsmBlkError(-1, "a view takes at most %d memtable runs" % MAX_MEM_RUNS)
+        self._mem_c = None
         self.l0 = [int(x) for x in l0]
         self.levels = [[int(x) for x in lv] for lv in levels]
         start = np.concatenate([[0], np.cumsum([len(lv) for lv in self.levels])]).astype(np.uint32)
@@ -252,8 +288,12 @@ class LsmView:
         self.level_start_t = batch._u32_table(start, device)
 
     def _c(self):
-        return LsmViewC(self.l0_t.data_ptr(), len(self.l0), len(self.levels), self.level_sst_t.data_ptr(),
-                        self.level_start_t.data_ptr())
+        cv = LsmViewC(self.l0_t.data_ptr(), len(self.l0), len(self.levels), self.level_sst_t.data_ptr(),
+                      self.level_start_t.data_ptr())
+        if self.nmem:
+            self._mem_c = self.mem._c()  # (the host struct the view points at lives as long as the view)
+            cv.mem, cv.mem_start, cv.nmem = ctypes.pointer(self._mem_c), self.mem_start_t.data_ptr(), self.nmem
+        return cv
 
 
 class SstSet:
@@ -261,7 +301,9 @@ class SstSet:
     file s = files[file_off[s]:file_off[s+1]], as sst_files returns them.  `files` is bytes, a numpy
     u8 array or a u8 tensor; `file_off` an int64 tensor or any sequence.  A call-wide error
     (lsmblk_sst_open_batch's stats[3]) raises LsmBlkError; an SST whose open failed keeps its flags
-    in err[s] and 0 blocks (lookups against it report ABSENT) while the others answer."""
+    in err[s] and 0 blocks (lookups against it report ABSENT) while the others answer.  No file at
+    all (files empty, file_off [0]) is a valid set: a database that has never flushed, read through
+    a view of memtable runs only."""
 
     def __init__(self, files, file_off, device="cuda", stream=None):
         dev = torch.device(device)
@@ -424,9 +466,10 @@ class SstSet:
         return out
 
     # ---- point reads over an LSM view
-    def view(self, l0, levels):
-        """An LsmView of this set: l0 = SST ids in priority order, levels = per level its ids in key order."""
-        return LsmView(l0, levels, self.device)
+    def view(self, l0, levels, mem=None):
+        """An LsmView of this set: l0 = SST ids in priority order, levels = per level its ids in key
+        order, mem = the memtable runs (mem_runs' result or its sources; None: a view of tables only)."""
+        return LsmView(l0, levels, self.device, mem)
 
     def lsm_get_into(self, view, qkeys, qkey_off, q_ts, nq, flags, res, stats, vals=None, val_cap=0, val_off=None):
         """Asynchronous lsmblk_lsm_get_batch over device tensors (no host sync): qkey_off int32 (u32),
@@ -466,7 +509,7 @@ class SstSet:
         return r, vals, (vo.cpu().numpy().view(np.uint32) if vo is not None else None), st
 
     def lsm_get(self, view, keys, read_ts, *, mvcc=False, newest=False, values=True):
-        """get_with_ts below the memtables for a batch of keys: key i at read_ts[i] (or the scalar
+        """get_with_ts (below the memtables for a view without runs) for a batch of keys: key i at read_ts[i] (or the scalar
         read_ts) over `view` -> dict of numpy arrays (status, src, sst, hit_blk, hit_ent, vlen, ts,
         val_pos, seeks, bloom_out) and, with `values`, "values" (the FOUND keys' value bytes, None for
         the others) and "val_off".  mvcc: the corrected landing per table; newest: the version with
@@ -633,7 +676,7 @@ class SstSet:
 
     def lsm_scan(self, view, lower, upper, *, lower_kind, upper_kind, read_ts=None, mvcc=False, sub_cap=None,
                  newest=False):
-        """scan_with_ts below the memtables for a batch of ranges over `view`: range i = (lower[i],
+        """scan_with_ts (below the memtables for a view without runs) for a batch of ranges over `view`: range i = (lower[i],
         upper[i]) with the bound kinds, at read_ts[i] (or the scalar read_ts) -> (dict of numpy arrays:
         status, sources, raw, merged, n; and per range the list of (key, ts, value)).  read_ts None:
         the merged stream, every version of every key's owning table.  newest
@@ -677,5 +720,6 @@ def open_compacted(r, device="cuda", stream=None):
 
 
 def view_sub_cap(view, nq):
-    """Table scans a batch of nq ranges over the view can expand into at most: every table, every range."""
-    return nq * (len(view.l0) + sum(len(lv) for lv in view.levels))
+    """Table scans a batch of nq ranges over the view can expand into at most: every memtable run and
+    every table, every range."""
+    return nq * (view.nmem + len(view.l0) + sum(len(lv) for lv in view.levels))
