@@ -14,7 +14,8 @@ ROOT = os.path.dirname(PKG)
 SO = os.path.join(PKG, "liblsmblk.so")
 DIAG_SO = os.path.join(PKG, "liblsmblk_diag.so")
 SOURCES = [os.path.join(PKG, "csrc", f) for f in ("lsmblk_gpu.hip", "lsmblk_compact.hip", "lsmblk_sst.hip", "lsmblk_get.hip", "lsmblk_host.cpp")]
-HEADERS = [os.path.join(ROOT, "include", "lsmblk.h"), os.path.join(PKG, "csrc", "lsmblk_dev.hpp")]
+HEADERS = [os.path.join(ROOT, "include", "lsmblk.h"), os.path.join(PKG, "csrc", "lsmblk_dev.hpp"),
+           os.path.join(PKG, "csrc", "lsmblk_keys.hpp")]
 
 
 def src_sha():

@@ -69,51 +69,7 @@ constexpr uint32_t kBigTT = 256;
 constexpr uint32_t kBigGrid = 1024;
 constexpr uint32_t kNone = 0xFFFFFFFFu;
 
-// ---------------------------------------------------------------- key access
-// Global keys through a bounds-checked descriptor over the key arena (reads past it give 0).
-struct GKeys {
-  rsrc_t r;
-  uint32_t lead;
-  __device__ __forceinline__ uint32_t dw(uint32_t pos) const {  // bytes [pos, pos + 4), LE
-    const uint32_t x = lead + pos, al = x & ~3u;
-    const uint32_t w0 = __builtin_amdgcn_raw_buffer_load_b32(r, al, 0, 0);
-    const uint32_t w1 = __builtin_amdgcn_raw_buffer_load_b32(r, al + 4, 0, 0);
-    return __builtin_amdgcn_alignbyte(w1, w0, x & 3);
-  }
-};
-__device__ __forceinline__ GKeys gkeys(const uint8_t* keys, uint32_t total) {
-  GKeys g;
-  g.lead = uint32_t(reinterpret_cast<uintptr_t>(keys) & 15);
-  g.r = make_rsrc(keys - g.lead, g.lead + total);
-  return g;
-}
-// LDS key image (unaligned ds_read_b32: the gfx9 unaligned access mode)
-struct LKeys {
-  const uint8_t* base;
-  __device__ __forceinline__ uint32_t dw(uint32_t pos) const {
-    return *reinterpret_cast<const uint32_t*>(base + pos);
-  }
-};
-
-// Lexicographic byte order of keys [a, a + la) and [b, b + lb) (src/key.rs:77-81 via Vec<u8>
-// Ord): -1, 0, 1.
-template <class KS>
-__device__ __forceinline__ int key_cmp(const KS& S, uint32_t a, uint32_t la, uint32_t b, uint32_t lb) {
-  const uint32_t m = la < lb ? la : lb;
-  for (uint32_t i = 0; i < m; i += 4) {
-    uint32_t x = S.dw(a + i), y = S.dw(b + i);
-    if (m - i < 4) {
-      const uint32_t mk = (1u << (8 * (m - i))) - 1;
-      x &= mk;
-      y &= mk;
-    }
-    if (x != y) {
-      const uint32_t z = __builtin_ctz(x ^ y) & ~7u;
-      return ((x >> z) & 0xFF) < ((y >> z) & 0xFF) ? -1 : 1;
-    }
-  }
-  return la < lb ? -1 : (la > lb ? 1 : 0);
-}
+// (key access, images and the key order: lsmblk_keys.hpp)
 
 // ---------------------------------------------------------------- merge
 struct MergeArgs {
@@ -184,51 +140,24 @@ __device__ __forceinline__ uint32_t find_run(const uint32_t* v, uint32_t nrun, u
   return lo;
 }
 
-// First 16 bytes of the key at arena position pos (len bytes) as big-endian words, zero padded:
-// five aligned dword loads through the descriptor (none straddles its bound) and alignbytes.
-__device__ __forceinline__ u32x4 key16(const GKeys& G, uint32_t pos, uint32_t len) {
-  const uint32_t x = G.lead + pos, al = x & ~3u, b = x & 3;
-  uint32_t w[5];
-#pragma unroll
-  for (uint32_t j = 0; j < 5; ++j) w[j] = __builtin_amdgcn_raw_buffer_load_b32(G.r, al + 4 * j, 0, 0);
-  uint32_t o[4];
-#pragma unroll
-  for (uint32_t i = 0; i < 4; ++i) {
-    uint32_t v = __builtin_amdgcn_alignbyte(w[i + 1], w[i], b);
-    const int32_t keep = int32_t(len) - int32_t(4 * i);  // bytes of this word inside the key
-    if (keep < 4) v &= keep <= 0 ? 0u : (1u << (8 * keep)) - 1;
-    o[i] = __builtin_bswap32(v);
-  }
-  return u32x4{o[0], o[1], o[2], o[3]};
-}
-
-// Key order on (16-byte prefix, length, global index): the prefixes decide unless equal and
-// both keys are longer than 16 bytes (then the tails are compared in global memory).
-__device__ __forceinline__ int kcmp16(const MergeArgs& a, const GKeys& G, const u32x4& x, uint32_t xl, uint32_t xg,
-                                      const u32x4& y, uint32_t yl, uint32_t yg) {
-  // two 64-bit compares, one branch (a branch per word compiled to divergent exec-mask code)
-  const uint64_t xh = (uint64_t(x.x) << 32) | x.y, xo = (uint64_t(x.z) << 32) | x.w;
-  const uint64_t yh = (uint64_t(y.x) << 32) | y.y, yo = (uint64_t(y.z) << 32) | y.w;
+// Key order on (image, length, global index) for the merge kernels, on the stored words themselves:
+// kPair false for big-endian words (k16, ck, cks), true for the LDS tiles' two u64 (KeyImage::pair).
+// The rule is image_cmp's (images, then lengths, then the tails in global memory); the merge kernels keep
+// it on u32x4 operands because through KeyImage values merge_tile_kernel and merge_big_kernel measured
+// 4 % slower (profiles/key_order_ab.json), as the tiles' branchy compare once did.
+template <bool kPair>
+__device__ __forceinline__ int merge_cmp(const MergeArgs& a, const ArenaKeys& G, const u32x4& x, uint32_t xl, uint32_t xg,
+                                         const u32x4& y, uint32_t yl, uint32_t yg) {
+  const uint64_t xh = kPair ? (uint64_t(x.y) << 32) | x.x : (uint64_t(x.x) << 32) | x.y;
+  const uint64_t xo = kPair ? (uint64_t(x.w) << 32) | x.z : (uint64_t(x.z) << 32) | x.w;
+  const uint64_t yh = kPair ? (uint64_t(y.y) << 32) | y.x : (uint64_t(y.x) << 32) | y.y;
+  const uint64_t yo = kPair ? (uint64_t(y.w) << 32) | y.z : (uint64_t(y.z) << 32) | y.w;
   const bool lt = xh < yh || (xh == yh && xo < yo);
   if (xh != yh || xo != yo) return lt ? -1 : 1;
   if (xl <= 16 || yl <= 16) return xl < yl ? -1 : (xl > yl ? 1 : 0);
   return key_cmp(G, a.key_off[xg] + 16, xl - 16, a.key_off[yg] + 16, yl - 16);
 }
-
-// The merge tiles keep each key's first 16 bytes in LDS as two u64 (most significant word first:
-// u32x4 {w1, w0, w3, w2} of the big-endian words), so that a compare is two 64-bit compares
-// without branches; kcmp16's chain of word compares compiled to a divergent branch per word
-// (exec-mask SALU around every step of every binary search, PMC: SALU 5.9e8 against VALU 7.3e8).
-__device__ __forceinline__ u32x4 k16_swap(const u32x4& k) { return u32x4{k.y, k.x, k.w, k.z}; }
-__device__ __forceinline__ int kcmp16s(const MergeArgs& a, const GKeys& G, const u32x4& x, uint32_t xl, uint32_t xg,
-                                       const u32x4& y, uint32_t yl, uint32_t yg) {
-  const uint64_t xh = (uint64_t(x.y) << 32) | x.x, xo = (uint64_t(x.w) << 32) | x.z;
-  const uint64_t yh = (uint64_t(y.y) << 32) | y.x, yo = (uint64_t(y.w) << 32) | y.z;
-  const bool lt = xh < yh || (xh == yh && xo < yo);
-  if (xh != yh || xo != yo) return lt ? -1 : 1;
-  if (xl <= 16 || yl <= 16) return xl < yl ? -1 : (xl > yl ? 1 : 0);
-  return key_cmp(G, a.key_off[xg] + 16, xl - 16, a.key_off[yg] + 16, yl - 16);
-}
+__device__ __forceinline__ u32x4 pair_of_be(const u32x4& k) { return u32x4{k.y, k.x, k.w, k.z}; }  // (KeyImage::be(k).u64_pair())
 
 // Every input key's first 16 bytes, once, in entry order (coalesced: the key arena is read front
 // to back): the merge tiles, the bound searches and the rules then read one 16-B word per key in
@@ -241,9 +170,9 @@ __global__ __launch_bounds__(256) void key16_kernel(const uint8_t* keys, const u
                                                     u32x4* k16, uint64_t* merr) {
   const uint64_t e = uint64_t(blockIdx.x) * 256 + threadIdx.x;
   if (e >= n) return;
-  const GKeys G = gkeys(keys, key_off[n]);
+  const ArenaKeys G(keys, key_off[n]);
   const uint32_t p = key_off[e], kl = key_off[e + 1] - p;
-  k16[e] = key16(G, p, kl);
+  k16[e] = image_of(G, p, kl).be_words();
   if (kl > 0xFFFFu) or_word(merr, LSMBLK_ERR_SEGMENTS);
 }
 
@@ -271,9 +200,9 @@ __global__ __launch_bounds__(256) void run_order_kernel(MergeArgs a) {
   if (g64 == 0 || g64 >= a.n) return;
   const uint32_t g = uint32_t(g64), r = find_run(s_rs, a.nrun, g);
   if (g == s_rs[r]) return;  // the first entry of its run (a bad run table: cand_rank_kernel reports it)
-  const GKeys K = gkeys(a.keys, a.key_off[a.n]);
+  const ArenaKeys K(a.keys, a.key_off[a.n]);
   const uint32_t p0 = a.key_off[g - 1], p1 = a.key_off[g], p2 = a.key_off[g + 1];
-  const int c = kcmp16(a, K, a.k16[g - 1], p1 - p0, g - 1, a.k16[g], p2 - p1, g);
+  const int c = merge_cmp<false>(a, K, a.k16[g - 1], p1 - p0, g - 1, a.k16[g], p2 - p1, g);
   if (c > 0 || (c == 0 && a.ts[g - 1] < a.ts[g])) or_err(a.mstats, LSMBLK_ERR_MALFORMED);
 }
 
@@ -289,7 +218,7 @@ __global__ __launch_bounds__(256) void cand_rank_kernel(MergeArgs a) {
     if (!ok) or_err(a.mstats, LSMBLK_ERR_SEGMENTS);
   }
   if (c >= NC) return;
-  const GKeys K = gkeys(a.keys, a.key_off[a.n]);
+  const ArenaKeys K(a.keys, a.key_off[a.n]);
   const uint32_t r = find_run(s_cb, a.nrun, c), j = c - s_cb[r];
   const uint32_t p = s_rs[r] + j * kMS;
   const u32x4 x = a.ck[c];
@@ -301,7 +230,7 @@ __global__ __launch_bounds__(256) void cand_rank_kernel(MergeArgs a) {
     uint32_t lo = 0, hi = s_cb[r2 + 1] - s_cb[r2];
     while (lo < hi) {
       const uint32_t mid = (lo + hi) >> 1, q = s_cb[r2] + mid;
-      const int cm = kcmp16(a, K, a.ck[q], a.cklen[q], s_rs[r2] + mid * kMS, x, xl, p);
+      const int cm = merge_cmp<false>(a, K, a.ck[q], a.cklen[q], s_rs[r2] + mid * kMS, x, xl, p);
       if (cm < 0 || (cm == 0 && r2 < r)) lo = mid + 1;
       else hi = mid;
     }
@@ -324,21 +253,21 @@ __global__ __launch_bounds__(256) void bounds_kernel(MergeArgs a) {
     *out = s_rs[r + 1];
     return;
   }
-  const GKeys K = gkeys(a.keys, a.key_off[a.n]);
+  const ArenaKeys K(a.keys, a.key_off[a.n]);
   const uint32_t x = a.cand[t], xl = a.ckslen[t];
   const u32x4 xk = a.cks[t];
   const uint32_t base = s_rs[r], C = s_cb[r + 1] - s_cb[r];
   uint32_t lo = 0, hi = C;  // first candidate of r with key >= x
   while (lo < hi) {
     const uint32_t mid = (lo + hi) >> 1, q = s_cb[r] + mid;
-    if (kcmp16(a, K, a.ck[q], a.cklen[q], base + mid * kMS, xk, xl, x) < 0) lo = mid + 1;
+    if (merge_cmp<false>(a, K, a.ck[q], a.cklen[q], base + mid * kMS, xk, xl, x) < 0) lo = mid + 1;
     else hi = mid;
   }
   uint32_t e0 = lo == 0 ? base : base + (lo - 1) * kMS + 1;
   uint32_t e1 = lo < C ? base + lo * kMS : s_rs[r + 1];
   while (e0 < e1) {  // first entry in [e0, e1) with key >= x (else e1)
     const uint32_t mid = (e0 + e1) >> 1;
-    if (kcmp16(a, K, a.k16[mid], a.key_off[mid + 1] - a.key_off[mid], mid, xk, xl, x) < 0) e0 = mid + 1;
+    if (merge_cmp<false>(a, K, a.k16[mid], a.key_off[mid + 1] - a.key_off[mid], mid, xk, xl, x) < 0) e0 = mid + 1;
     else e1 = mid;
   }
   *out = e0;
@@ -353,7 +282,7 @@ struct TileHdr {
 template <uint32_t E>
 struct alignas(16) MTileLdsT {
   TileHdr h;
-  u32x4 kw[E];          // first 16 key bytes as big-endian words, zero padded, in kcmp16s order
+  u32x4 kw[E];          // first 16 key bytes, zero padded, as two u64 (KeyImage::pair)
   uint16_t klen[E];        // (key lengths are u16 in the block format)
   uint16_t sp[E + 1];   // survivor prefix over the tile (run-major order)
   uint8_t surv[E];
@@ -391,7 +320,7 @@ struct TwoEnd {
   uint32_t len, g, pos;
   bool nonempty, inf;
 };
-__device__ __forceinline__ TwoEnd two_end(const MergeArgs& a, const GKeys& G) {
+__device__ __forceinline__ TwoEnd two_end(const MergeArgs& a, const ArenaKeys& G) {
   TwoEnd t{};
   const uint32_t e0 = a.run_start[a.nrun - 1], e1 = a.run_start[a.nrun];
   t.nonempty = e1 > e0 && a.two_end != LSMBLK_TWO_END_BELOW;
@@ -401,18 +330,18 @@ __device__ __forceinline__ TwoEnd two_end(const MergeArgs& a, const GKeys& G) {
     t.g = e1 - 1;
     t.pos = a.key_off[t.g];
     t.len = a.key_off[t.g + 1] - t.pos;
-    t.k16 = key16(G, t.pos, t.len);
+    t.k16 = image_of(G, t.pos, t.len).be_words();
   }
   return t;
 }
 
 // Every tile entry's first 16 key bytes and length into LDS.
 template <uint32_t E, uint32_t T>
-__device__ __forceinline__ void load_tile_keys(const MergeArgs& a, MTileLdsT<E>& L, const GKeys& G) {
+__device__ __forceinline__ void load_tile_keys(const MergeArgs& a, MTileLdsT<E>& L, const ArenaKeys& G) {
   const TileHdr& H = L.h;
   for (uint32_t u = threadIdx.x; u < H.total; u += T) {
     const uint32_t r = find_run(H.tb, a.nrun, u), g = H.lo[r] + u - H.tb[r];
-    L.kw[u] = k16_swap(a.k16[g]);  // (kcmp16s form)
+    L.kw[u] = pair_of_be(a.k16[g]);
     L.klen[u] = uint16_t(a.key_off[g + 1] - a.key_off[g]);
   }
 }
@@ -459,7 +388,7 @@ template <uint32_t E, uint32_t T, bool NEWEST>
 __device__ void merge_tile_lds(const MergeArgs& a, MTileLdsT<E>& L, uint32_t t) {
   TileHdr& H = L.h;
   const uint32_t tid = threadIdx.x, nrun = a.nrun, total = H.total;
-  const GKeys G = gkeys(a.keys, a.key_off[a.n]);
+  const ArenaKeys G(a.keys, a.key_off[a.n]);
   load_tile_keys<E, T>(a, L, G);
   __syncthreads();
   if constexpr (NEWEST) {
@@ -475,7 +404,7 @@ __device__ void merge_tile_lds(const MergeArgs& a, MTileLdsT<E>& L, uint32_t t) 
         uint32_t lo = 0, hi = H.tb[r2 + 1] - b;
         while (lo < hi) {
           const uint32_t mid = (lo + hi) >> 1;
-          const int c = kcmp16s(a, G, L.kw[b + mid], L.klen[b + mid], g2 + mid, x, xl, g);
+          const int c = merge_cmp<true>(a, G, L.kw[b + mid], L.klen[b + mid], g2 + mid, x, xl, g);
           bool before = c < 0;
           if (c == 0) {
             const uint64_t tm = a.ts[g2 + mid];
@@ -497,7 +426,7 @@ __device__ void merge_tile_lds(const MergeArgs& a, MTileLdsT<E>& L, uint32_t t) 
     uint32_t lo = 0, hi = H.tb[r2 + 1] - b;
     while (lo < hi) {
       const uint32_t mid = (lo + hi) >> 1;
-      const int c = kcmp16s(a, G, L.kw[b + mid], L.klen[b + mid], H.lo[r2] + mid, x, xl, xg);
+      const int c = merge_cmp<true>(a, G, L.kw[b + mid], L.klen[b + mid], H.lo[r2] + mid, x, xl, xg);
       if (c < 0 || (upper && c == 0)) lo = mid + 1;
       else hi = mid;
     }
@@ -506,7 +435,7 @@ __device__ void merge_tile_lds(const MergeArgs& a, MTileLdsT<E>& L, uint32_t t) 
   const uint32_t B = nrun - 1;
   TwoEnd te{};
   if (a.two) te = two_end(a, G);
-  const u32x4 tek = k16_swap(te.k16);
+  const u32x4 tek = pair_of_be(te.k16);
   // phase A: survival -- no lower-index run holds the key (MergeIterator advances those heads)
   for (uint32_t u = tid; u < total; u += T) {
     const uint32_t r = find_run(H.tb, nrun, u), g = H.lo[r] + u - H.tb[r];
@@ -515,12 +444,12 @@ __device__ void merge_tile_lds(const MergeArgs& a, MTileLdsT<E>& L, uint32_t t) 
     bool held = false;
     for (uint32_t r2 = 0; r2 < r && !held; ++r2) {
       const uint32_t p = bound(r2, x, xl, g, false), b = H.tb[r2];
-      held = p < H.tb[r2 + 1] - b && kcmp16s(a, G, L.kw[b + p], L.klen[b + p], H.lo[r2] + p, x, xl, g) == 0;
+      held = p < H.tb[r2 + 1] - b && merge_cmp<true>(a, G, L.kw[b + p], L.klen[b + p], H.lo[r2] + p, x, xl, g) == 0;
     }
     uint32_t sv = !held;
     if (a.two) {
       if (r == B) sv = held ? ((u - H.tb[B]) - bound(B, x, xl, g, false)) & 1u : 1u;  // skip_b
-      else sv = sv && te.nonempty && (te.inf || kcmp16s(a, G, x, xl, g, tek, te.len, te.g) < 0);
+      else sv = sv && te.nonempty && (te.inf || merge_cmp<true>(a, G, x, xl, g, tek, te.len, te.g) < 0);
     }
     L.surv[u] = uint8_t(sv);
   }
@@ -554,7 +483,7 @@ __device__ void merge_tile_lds(const MergeArgs& a, MTileLdsT<E>& L, uint32_t t) 
 template <bool NEWEST>
 __device__ void merge_tile_global(const MergeArgs& a, TileHdr& H, uint32_t* rsv, uint32_t t) {  // rsv: LDS, kMaxRuns
   const uint32_t l = lane_id(), nrun = a.nrun, total = H.total;
-  const GKeys G = gkeys(a.keys, a.key_off[a.n]);
+  const ArenaKeys G(a.keys, a.key_off[a.n]);
   auto kpos = [&](uint32_t r, uint32_t k, uint32_t& len) -> uint32_t {
     const uint32_t g = H.lo[r] + k, p = a.key_off[g];
     len = a.key_off[g + 1] - p;
@@ -818,60 +747,17 @@ struct GatherArgs {
   uint32_t* kidx;           // per kept entry, its input index (or null)
 };
 
-// Byte order of key (x, xl) against a range bound (y, yl) in device memory: -1, 0, 1.
-__device__ __forceinline__ int bound_cmp(const uint8_t* x, uint32_t xl, const uint8_t* y, uint32_t yl) {
-  const uint32_t m = xl < yl ? xl : yl;
-  for (uint32_t t = 0; t < m; ++t)
-    if (x[t] != y[t]) return x[t] < y[t] ? -1 : 1;
-  return xl < yl ? -1 : (xl > yl ? 1 : 0);
+__device__ __forceinline__ KeyPtr gather_key(const GatherArgs& a, uint32_t i) {
+  return KeyPtr{a.keys + a.key_off[i], a.key_off[i + 1] - a.key_off[i]};
 }
 
 // lo <= key < hi.  The bounds are user keys, so all the versions of a key fall on one side.
 __device__ __forceinline__ bool in_range(const GatherArgs& a, uint32_t i) {
   if (!a.range.has_lo && !a.range.has_hi) return true;
-  const uint32_t k0 = a.key_off[i], kl = a.key_off[i + 1] - k0;
-  if (a.range.has_lo && bound_cmp(a.keys + k0, kl, a.range.lo, a.range.lo_len) < 0) return false;
-  if (a.range.has_hi && bound_cmp(a.keys + k0, kl, a.range.hi, a.range.hi_len) >= 0) return false;
+  const KeyPtr k = gather_key(a, i);
+  if (a.range.has_lo && byte_cmp(k, KeyPtr{a.range.lo, a.range.lo_len}) < 0) return false;
+  if (a.range.has_hi && byte_cmp(k, KeyPtr{a.range.hi, a.range.hi_len}) >= 0) return false;
   return true;
-}
-
-__device__ __forceinline__ bool same_key_g(const GatherArgs& a, uint32_t i, uint32_t j) {
-  const uint32_t a0 = a.key_off[i], al = a.key_off[i + 1] - a0;
-  const uint32_t b0 = a.key_off[j], bl = a.key_off[j + 1] - b0;
-  if (al != bl) return false;
-  uint32_t x = 0;
-  for (; x + 16 <= al; x += 16) {
-    const u32x4 p = *reinterpret_cast<const u32x4*>(a.keys + a0 + x);
-    const u32x4 q = *reinterpret_cast<const u32x4*>(a.keys + b0 + x);
-    if (p.x != q.x || p.y != q.y || p.z != q.z || p.w != q.w) return false;
-  }
-  for (; x < al; ++x)
-    if (a.keys[a0 + x] != a.keys[b0 + x]) return false;
-  return true;
-}
-
-// Byte order of the keys at arena positions (pa, la) and (pb, lb), x / y their first 16 bytes
-// (k16): those decide unless equal with both keys longer (then the tails, in global memory).
-__device__ __forceinline__ int key_cmp16(const GKeys& G, const u32x4& x, uint32_t pa, uint32_t la, const u32x4& y,
-                                         uint32_t pb, uint32_t lb) {
-  const uint64_t xh = (uint64_t(x.x) << 32) | x.y, xo = (uint64_t(x.z) << 32) | x.w;  // (as kcmp16)
-  const uint64_t yh = (uint64_t(y.x) << 32) | y.y, yo = (uint64_t(y.z) << 32) | y.w;
-  const bool lt = xh < yh || (xh == yh && xo < yo);
-  if (xh != yh || xo != yo) return lt ? -1 : 1;
-  if (la <= 16 || lb <= 16) return la < lb ? -1 : (la > lb ? 1 : 0);
-  return key_cmp(G, pa + 16, la - 16, pb + 16, lb - 16);
-}
-
-__device__ __forceinline__ bool prefix_filtered(const GatherArgs& a, uint32_t i) {
-  const uint32_t k0 = a.key_off[i], kl = a.key_off[i + 1] - k0;
-  for (uint32_t f = 0; f < a.npfx; ++f) {
-    const uint32_t f0 = a.pfx_off[f], fl = a.pfx_off[f + 1] - f0;
-    if (fl > kl) continue;
-    bool m = true;
-    for (uint32_t x = 0; x < fl && m; ++x) m = a.pfx[f0 + x] == a.keys[k0 + x];
-    if (m) return true;
-  }
-  return false;
 }
 
 // Two-level merge order: a key's versions are not newest first (b's versions come before a's), so
@@ -884,12 +770,13 @@ __global__ __launch_bounds__(256) void mgroup_kernel(GatherArgs a) {
   const uint64_t N = *a.nm;
   const uint64_t j0 = uint64_t(blockIdx.x) * 256 + threadIdx.x;
   if (j0 >= N) return;
-  if (j0 > 0 && a.perm[j0] < a.n_max && a.perm[j0 - 1] < a.n_max && same_key_g(a, a.perm[j0 - 1], a.perm[j0]))
+  if (j0 > 0 && a.perm[j0] < a.n_max && a.perm[j0 - 1] < a.n_max &&
+      key_equal(gather_key(a, a.perm[j0 - 1]), gather_key(a, a.perm[j0])))
     return;
   bool lk = false, fkbw = true;  // last_key == this key; first_key_below_watermark
   for (uint64_t j = j0; j < N; ++j) {
     const uint32_t i = a.perm[j];
-    if (i >= a.n_max || (j > j0 && !same_key_g(a, a.perm[j - 1], i))) break;
+    if (i >= a.n_max || (j > j0 && !key_equal(gather_key(a, a.perm[j - 1]), gather_key(a, i)))) break;
     const bool same = lk, below = a.ts[i] <= a.wm, empty = a.val_off[i + 1] == a.val_off[i];
     if (!same) fkbw = true;
     bool kept = false;
@@ -898,7 +785,7 @@ __global__ __launch_bounds__(256) void mgroup_kernel(GatherArgs a) {
       fkbw = false;
     } else if (!(below && same && !fkbw)) {     // :256-260
       if (below) fkbw = false;
-      if (!(below && prefix_filtered(a, i))) {  // :262-275
+      if (!(below && has_any_prefix(gather_key(a, i), a.pfx, a.pfx_off, a.npfx))) {  // :262-275
         kept = true;
         lk = true;                              // :294-297
       }
@@ -909,7 +796,7 @@ __global__ __launch_bounds__(256) void mgroup_kernel(GatherArgs a) {
 
 __global__ __launch_bounds__(256) void mflag_kernel(GatherArgs a) {
   const uint64_t N = *a.nm;
-  const GKeys G = gkeys(a.keys, a.key_off[a.n_max]);
+  const ArenaKeys G(a.keys, a.key_off[a.n_max]);
   // Every thread loads its own merged entry (input index, key position and length, first 16 key
   // bytes, value length, ts) once and takes its merged predecessor's from the neighbouring thread
   // through LDS (thread 0 loads its predecessor): half the gathers of loading both per thread.
@@ -969,7 +856,8 @@ __global__ __launch_bounds__(256) void mflag_kernel(GatherArgs a) {
     bool ordered = iv && ip < a.n_max;
     int cmp = -1;
     if (ordered && j > 0) {
-      cmp = key_cmp16(G, p16, p0, pl, x16, k0, kl);
+      cmp = image_cmp(KeyImage::be(p16), pl, KeyImage::be(x16), kl,
+                      [&] { return key_cmp(G, p0 + 16, pl - 16, k0 + 16, kl - 16); });
       ordered = cmp <= 0;
     }
     if (ordered) {
@@ -986,7 +874,7 @@ __global__ __launch_bounds__(256) void mflag_kernel(GatherArgs a) {
         const bool start = !(j > 0 && cmp == 0);
         if (!start && tsp <= a.wm) k = false;               // a later version at or below the watermark
         else if (a.bottom && start && vl == 0) k = false;   // :244-254
-        else k = !(a.npfx && prefix_filtered(a, i));        // CompactionFilter::Prefix, :264-275
+        else k = !has_any_prefix(KeyPtr{a.keys + k0, kl}, a.pfx, a.pfx_off, a.npfx);  // CompactionFilter::Prefix, :264-275
       }
     } else {
       or_err(a.stats, LSMBLK_ERR_MALFORMED);
@@ -1371,53 +1259,6 @@ constexpr uint32_t kShardWords = 16;  // [8, 12): the encode's stats
 
 __device__ __forceinline__ uint64_t rot_n(const RotArgs& a) { return uni64(*a.dn); }
 
-// LCP of keys (pp, pl) and (kp, kl) through the descriptor; *less = key p < key k (byte order)
-__device__ __forceinline__ uint32_t glcp(const GKeys& K, uint32_t pp, uint32_t pl, uint32_t kp, uint32_t kl,
-                                         int* order) {
-  const uint32_t m = pl < kl ? pl : kl;
-  for (uint32_t i = 0; i < m; i += 4) {
-    uint32_t x = K.dw(pp + i), y = K.dw(kp + i);
-    if (m - i < 4) {
-      const uint32_t mk = (1u << (8 * (m - i))) - 1;
-      x &= mk;
-      y &= mk;
-    }
-    if (x != y) {
-      const uint32_t z = __builtin_ctz(x ^ y) & ~7u;
-      if (order) *order = ((x >> z) & 0xFF) < ((y >> z) & 0xFF) ? -1 : 1;
-      return i + (z >> 3);
-    }
-  }
-  if (order) *order = pl < kl ? -1 : (pl > kl ? 1 : 0);
-  return m;
-}
-
-// LCP of two keys from their first 16 bytes (big-endian words, zero padded) and, past a tie on
-// those, the tails at arena positions pp / kp; *order as glcp's (the first key against the second).
-__device__ __forceinline__ uint32_t lcp_k16(const GKeys& G, const u32x4& x, uint32_t pp, uint32_t pl, const u32x4& y,
-                                          uint32_t kp, uint32_t kl, int* order) {
-  const uint32_t m = pl < kl ? pl : kl;
-  const uint32_t xs[4] = {x.x, x.y, x.z, x.w}, ys[4] = {y.x, y.y, y.z, y.w};
-#pragma unroll
-  for (uint32_t w = 0; w < 4; ++w) {
-    if (xs[w] != ys[w]) {
-      const uint32_t z = 4 * w + (__builtin_clz(xs[w] ^ ys[w]) >> 3);
-      if (z < m) {
-        const uint32_t sh = 24 - 8 * (z & 3);
-        *order = ((xs[w] >> sh) & 0xFF) < ((ys[w] >> sh) & 0xFF) ? -1 : 1;
-        return z;
-      }
-      *order = pl < kl ? -1 : (pl > kl ? 1 : 0);  // (a zero pad against a key byte)
-      return m;
-    }
-  }
-  if (m <= 16) {
-    *order = pl < kl ? -1 : (pl > kl ? 1 : 0);
-    return m;
-  }
-  return 16 + glcp(G, pp + 16, pl - 16, kp + 16, kl - 16, order);
-}
-
 __global__ __launch_bounds__(256) void rot_adj_kernel(RotArgs a) {
   const uint64_t n = rot_n(a);
   const uint32_t t = threadIdx.x;
@@ -1457,10 +1298,16 @@ __global__ __launch_bounds__(256) void rot_adj_kernel(RotArgs a) {
         pl = a.key_off[e] - a.key_off[e - 1];
         p16 = a.k16[ip];
       }
-      const GKeys K = gkeys(a.akeys, a.akey_off[a.an]);
-      const bool tie = pl > 16 && kl > 16 && p16.x == x16.x && p16.y == x16.y && p16.z == x16.z && p16.w == x16.w;
+      const ArenaKeys K(a.akeys, a.akey_off[a.an]);
+      const KeyImage pm = KeyImage::be(p16), xm = KeyImage::be(x16);
+      const bool tie = pl > 16 && kl > 16 && pm == xm;  // (the positions' loads issue ahead of the compare)
+      const uint32_t pp = tie ? a.akey_off[ip] : 0u, kp = tie ? a.akey_off[i] : 0u;
       int ord = 0;
-      const uint32_t lcp = lcp_k16(K, p16, tie ? a.akey_off[ip] : 0u, pl, x16, tie ? a.akey_off[i] : 0u, kl, &ord);
+      const uint32_t lcp = image_lcp(pm, pl, xm, kl, ord, [&](int& o) {
+        const KeyDiff d = key_diff(K, pp + 16, pl - 16, kp + 16, kl - 16);
+        o = d.order;
+        return d.lcp;
+      });
       const bool same = a.ksame ? a.ksame[e] != 0 : ord == 0;
       al = (lcp < kRotLcp ? lcp : kRotLcp) | (ord > 0 ? kRotUnsorted : 0u) | (same ? kRotSame : 0u);
     }
@@ -1472,12 +1319,11 @@ __global__ __launch_bounds__(256) void rot_adj_kernel(RotArgs a) {
   a.rec[e] = kl + (a.val_off[e + 1] - a.val_off[e]);
   uint32_t al = 0;
   if (e > 0) {
-    const GKeys K = gkeys(a.keys, a.key_off[n]);
+    const ArenaKeys K(a.keys, a.key_off[n]);
     const uint32_t pp = a.key_off[e - 1], pl = kp - pp;
-    int ord = 0;
-    const uint32_t lcp = glcp(K, pp, pl, kp, kl, &ord);
-    const bool same = a.ksame ? a.ksame[e] != 0 : ord == 0;
-    al = (lcp < kRotLcp ? lcp : kRotLcp) | (ord > 0 ? kRotUnsorted : 0u) | (same ? kRotSame : 0u);
+    const KeyDiff d = key_diff(K, pp, pl, kp, kl);
+    const bool same = a.ksame ? a.ksame[e] != 0 : d.order == 0;
+    al = (d.lcp < kRotLcp ? d.lcp : kRotLcp) | (d.order > 0 ? kRotUnsorted : 0u) | (same ? kRotSame : 0u);
   }
   a.alcp[e] = al;
 }
@@ -1513,7 +1359,7 @@ __global__ __launch_bounds__(256) void rot_next_kernel(RotArgs a) {
     uint32_t pmin = kRotLcp;
     bool direct = false, stop = false;
     uint32_t sp = 0, sl = 0;
-    GKeys K;
+    ArenaKeys K;
     uint64_t e = s + 1;
     // Fast walk: sorted pairs inside the LDS window, kRotStep entries' (rec, alcp) read ahead of
     // their use.  (A loop reading `in window ? LDS : global` was if-converted into a global load
@@ -1557,7 +1403,7 @@ __global__ __launch_bounds__(256) void rot_next_kernel(RotArgs a) {
       uint32_t p;
       if (!direct && (al & kRotUnsorted)) {  // LCP vs the first key directly from here on
         direct = true;
-        K = gkeys(a.keys, a.key_off[n]);
+        K = ArenaKeys(a.keys, a.key_off[n]);
         sp = a.key_off[s];
         sl = a.key_off[s + 1] - sp;
       }
@@ -1566,7 +1412,7 @@ __global__ __launch_bounds__(256) void rot_next_kernel(RotArgs a) {
         p = pmin;
       } else {
         const uint32_t kp = a.key_off[e];
-        p = glcp(K, sp, sl, kp, a.key_off[e + 1] - kp, nullptr);
+        p = key_diff(K, sp, sl, kp, a.key_off[e + 1] - kp).lcp;
       }
       before += uint64_t(r) + 16 - p;
     }
@@ -1657,7 +1503,7 @@ __global__ __launch_bounds__(256) void rot_double2_kernel(RotArgs a, uint32_t k)
   or_need(a.need + k + 1, short2);
 }
 
-// Highest block-chain level computed (J / S levels 0 .. top).// Highest block-chain level computed (J / S levels 0 .. top).
+// Highest block-chain level computed (J / S levels 0 .. top).
 __device__ __forceinline__ uint32_t rot_top(const RotArgs& a) {
   uint32_t kc = 1;
   while (kc < a.levels && a.need[kc - 1]) ++kc;

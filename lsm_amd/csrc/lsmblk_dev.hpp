@@ -1,5 +1,6 @@
 // lsmblk_dev.hpp -- shared by the HIP translation units of liblsmblk.so: wave primitives,
-// buffer-descriptor helpers, look-back granules (device) and the context struct (host).
+// buffer-descriptor helpers, the key order (lsmblk_keys.hpp), look-back granules (device) and the
+// context struct (host).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -14,12 +15,9 @@
 #include <vector>
 
 #include "lsmblk.h"
+#include "lsmblk_keys.hpp"  // (u32x4, rsrc_t, make_rsrc and the key order)
 
 namespace {
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef __amdgpu_buffer_rsrc_t rsrc_t;
 
 constexpr uint32_t kSpinLimit = 1u << 22;  // look-back bound (~seconds); never reached when correct
 
@@ -118,14 +116,6 @@ __device__ __forceinline__ T wave_sum(T v) {
     for (uint32_t d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
     return v;
   }
-}
-__device__ __forceinline__ rsrc_t make_rsrc(const void* p16, uint32_t nbytes) {
-  const uint32_t n = nbytes >= 0xFFFFFFF0u ? 0xFFFFFFFFu : (nbytes + 15) & ~15u;
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p16), (short)0, (int)n, 0x00020000);
-}
-// Store descriptor with an exact byte bound: an access reaching past nbytes is dropped.
-__device__ __forceinline__ rsrc_t make_rsrc_exact(void* p16, uint32_t nbytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(p16, (short)0, (int)nbytes, 0x00020000);
 }
 __device__ __forceinline__ uint32_t bswap16(uint32_t v) { return ((v & 0xFF) << 8) | ((v >> 8) & 0xFF); }
 
@@ -376,7 +366,7 @@ __host__ __device__ __forceinline__ uint32_t fmur(uint32_t a, uint32_t h) {
 }
 
 // Src: a byte source with u32 fetches at arbitrary offsets (bytes [i, i + 4), little-endian)
-// and single bytes.
+// and single bytes (KeyRef).
 template <class Src>
 __host__ __device__ uint32_t fingerprint32(const Src& S, uint32_t len) {
   if (len <= 4) {

@@ -198,15 +198,8 @@ __global__ __launch_bounds__(64) void sst_open_walk_kernel(OpenArgs a) {
       bad = true;
       break;
     }
-    uint64_t hi = 0, lo = 0;
-    if (fl) {
-      const uint32_t m = fl < 16 ? fl : 16;
-      const uint8_t* k = need(kpos, m);
-      for (uint32_t j = 0; j < m; ++j) {
-        if (j < 8) hi |= uint64_t(k[j]) << (56 - 8 * j);
-        else lo |= uint64_t(k[j]) << (56 - 8 * (j - 8));
-      }
-    }
+    KeyImage fm{0, 0};
+    if (fl) fm = image_of_bytes(need(kpos, fl < 16 ? fl : 16), fl);
     const uint32_t ll = be16w(kpos + fl + 8);
     const uint64_t lpos = kpos + fl + 8 + 2;
     if (lpos + ll + 8 > rec_end) {
@@ -220,8 +213,8 @@ __global__ __launch_bounds__(64) void sst_open_walk_kernel(OpenArgs a) {
     }
     if (l == 0) {
       lsmblk_sst_index rec;
-      rec.img_hi = hi;
-      rec.img_lo = lo;
+      rec.img_hi = fm.hi;
+      rec.img_lo = fm.lo;
       rec.off = off;
       rec.end = uint32_t(mo);  // the last block ends at the meta section; patched by the next record
       rec.key_pos = uint32_t(kpos);
@@ -327,19 +320,7 @@ struct GetArgs : OpenedSet, PointArgs {
   lsmblk_get_result* res;
 };
 
-// The query key through a bounds-checked descriptor over the arena up to the key's end (rounded up
-// to the aligned dword that holds its last byte): aligned dword loads, past the bound they read 0.
-struct QKey {
-  rsrc_t r;
-  uint32_t x;  // descriptor byte of the key's first byte
-  uint32_t len;
-  __device__ __forceinline__ uint32_t fetch(uint32_t i) const {
-    const uint32_t y = x + i, al = y & ~3u;
-    return __builtin_amdgcn_alignbyte(__builtin_amdgcn_raw_buffer_load_b32(r, al + 4, 0, 0),
-                                      __builtin_amdgcn_raw_buffer_load_b32(r, al, 0, 0), y & 3);
-  }
-  __device__ __forceinline__ uint32_t byte(uint32_t i) const { return __builtin_amdgcn_raw_buffer_load_b8(r, x + i, 0, 0); }
-};
+using QKey = KeyRef<ArenaKeys>;  // the query key, through key_upto (lsmblk_keys.hpp)
 
 // key order of the first nv (1..4) bytes of two little-endian dword loads
 __device__ __forceinline__ int cmp_dw(uint32_t x, uint32_t y, uint32_t nv) {
@@ -372,17 +353,6 @@ __device__ __forceinline__ int wave_cmp(FA fa, uint32_t la, const QKey& q, uint3
   return la < q.len ? -1 : (la > q.len ? 1 : 0);
 }
 
-// Key order of file bytes p[0 .. la) against the query by one lane (the block search's fallback
-// among equal first-key images).
-__device__ int lane_cmp(const uint8_t* p, uint32_t la, const QKey& q) {
-  const uint32_t mn = la < q.len ? la : q.len;
-  for (uint32_t i = 0; i < mn; ++i) {
-    const uint32_t x = p[i], y = q.byte(i);
-    if (x != y) return x < y ? -1 : 1;
-  }
-  return la < q.len ? -1 : (la > q.len ? 1 : 0);
-}
-
 // First index of [lo, hi) where pred turns false (hi: nowhere), pred true on a prefix of the range:
 // 64 probes a step, one per lane, so a step cuts the range 65-fold for one round trip.
 template <class Pred>
@@ -402,40 +372,19 @@ __device__ __forceinline__ uint32_t kary_first_false(uint32_t lo, uint32_t hi, P
   return uni(lo + uint32_t(__builtin_popcountll(__ballot(p))));
 }
 
-// The query's leading 16 bytes as the index records hold a first key's (zero-padded, big-endian).
-__device__ __forceinline__ void query_image(const QKey& q, uint64_t& qhi, uint64_t& qlo) {
-  uint32_t w[4];
-#pragma unroll
-  for (uint32_t j = 0; j < 4; ++j) {
-    const uint32_t nv = q.len > 4 * j ? q.len - 4 * j : 0u;
-    const uint32_t v = __builtin_bswap32(q.fetch(4 * j));
-    w[j] = nv >= 4 ? v : (nv ? v & ~(~0u >> (8 * nv)) : 0u);
-  }
-  qhi = (uint64_t(w[0]) << 32) | w[1];
-  qlo = (uint64_t(w[2]) << 32) | w[3];
-}
-
 // partition_point of an SST's block first keys against the query: the blocks with first_key <= q
 // (strict: < q), by the k-ary search over the first-key images; blocks whose image equals the
 // query's, [iL, iU), compare whole keys.
 __device__ __forceinline__ uint32_t index_partition(const lsmblk_sst_index* ix, const uint8_t* F, uint32_t nblk,
                                                     const QKey& q, bool strict) {
-  uint64_t qhi, qlo;
-  query_image(q, qhi, qlo);
-  const uint32_t iL = kary_first_false(0, nblk, [&](uint32_t i) {
-    const u32x4 v = *reinterpret_cast<const u32x4*>(ix + i);
-    const uint64_t hi = (uint64_t(v.y) << 32) | v.x, lo = (uint64_t(v.w) << 32) | v.z;
-    return hi < qhi || (hi == qhi && lo < qlo);
-  });
-  const uint32_t iU = kary_first_false(iL, nblk, [&](uint32_t i) {
-    const u32x4 v = *reinterpret_cast<const u32x4*>(ix + i);
-    const uint64_t hi = (uint64_t(v.y) << 32) | v.x, lo = (uint64_t(v.w) << 32) | v.z;
-    return hi < qhi || (hi == qhi && lo <= qlo);
-  });
+  const KeyImage qm = image_of(q);  // (the index records hold each first key's image: img_hi, img_lo)
+  auto img = [&](uint32_t i) { return KeyImage::pair(*reinterpret_cast<const u32x4*>(ix + i)); };
+  const uint32_t iL = kary_first_false(0, nblk, [&](uint32_t i) { return img(i) < qm; });
+  const uint32_t iU = kary_first_false(iL, nblk, [&](uint32_t i) { return img(i) <= qm; });
   uint32_t P = iL;
   if (iU > iL)
     P = kary_first_false(iL, iU, [&](uint32_t i) {
-      const int c = lane_cmp(F + ix[i].key_pos, ix[i].key_len, q);
+      const int c = byte_cmp(KeyPtr{F + ix[i].key_pos, ix[i].key_len}, q);
       return strict ? c < 0 : c <= 0;
     });
   return P;
@@ -710,8 +659,6 @@ __global__ __launch_bounds__(64 * kGetWaves) __attribute__((amdgpu_waves_per_eu(
   const uint32_t l = lane_id();
   uint8_t* const S = img[wave_id()];
   const bool mvcc = (a.flags & LSMBLK_GET_MVCC) != 0, filter = !(a.flags & LSMBLK_GET_NO_FILTER);
-  const uint32_t qlead = uint32_t(reinterpret_cast<uintptr_t>(a.qkeys) & 3);
-  const uint8_t* const qbase = a.qkeys - qlead;
   const OpenedSet& o = a;
   uint32_t err = 0, nfound = 0;
   if (blockIdx.x == 0 && threadIdx.x == 0) a.stats[0] = a.nq;
@@ -729,7 +676,7 @@ __global__ __launch_bounds__(64 * kGetWaves) __attribute__((amdgpu_waves_per_eu(
         err |= LSMBLK_ERR_EMPTY_KEY;
         break;
       }
-      const QKey q{make_rsrc_exact(const_cast<uint8_t*>(qbase), (qlead + k1 + 3) & ~3u), qlead + k0, k1 - k0};
+      const QKey q = key_upto(a.qkeys, k0, k1);
       QHash qh{0, false};
       if (sst_lookup(o, s, q, uni64(a.q_ts[qi]), mvcc, filter, S, qh, k)) err |= LSMBLK_ERR_MALFORMED;
     } while (false);
@@ -761,14 +708,6 @@ struct LsmGetArgs : OpenedSet, ViewArgs, PointArgs {
   lsmblk_lsm_get_result* res;
   uint32_t* vflag;
 };
-
-// key order of file bytes a[0 .. la) against b[0 .. lb) by one lane
-__device__ int lane_cmp2(const uint8_t* x, uint32_t la, const uint8_t* y, uint32_t lb) {
-  const uint32_t mn = la < lb ? la : lb;
-  for (uint32_t i = 0; i < mn; ++i)
-    if (x[i] != y[i]) return x[i] < y[i] ? -1 : 1;
-  return la < lb ? -1 : (la > lb ? 1 : 0);
-}
 
 // The view against the opened set, one lane per view entry (the L0 ids, then the level ids):
 // level_start (and mem_start, which bounds every read of a memtable run, against mem->n) first, by
@@ -814,7 +753,8 @@ __global__ __launch_bounds__(256) void lsm_view_check_kernel(ViewCheckArgs a) {
       const uint32_t u = a.level_sst[j + 1];
       if (u >= a.nsst || a.desc[u].err || a.desc[u].nblk == 0) continue;  // (flagged by its own lane)
       const lsmblk_sst_desc* e = a.desc + u;
-      if (lane_cmp2(a.files + d->last_key_pos, d->last_key_len, a.files + e->first_key_pos, e->first_key_len) >= 0)
+      if (byte_cmp(KeyPtr{a.files + d->last_key_pos, d->last_key_len},
+                   KeyPtr{a.files + e->first_key_pos, e->first_key_len}) >= 0)
         err |= LSMBLK_ERR_MALFORMED;
     }
   }
@@ -828,11 +768,10 @@ __global__ __launch_bounds__(256) void lsm_view_check_kernel(ViewCheckArgs a) {
 // first_key <= q, counted as index_partition counts blocks -- a table's first key is its first
 // block's, so index[desc[t].blk0] holds its image; whole keys only inside the image tie range.
 // Table t's image against the query's: 1 = below it, 2 = not above it.
-__device__ __forceinline__ uint32_t table_img_le(const OpenedSet& o, uint32_t nsst, uint32_t t, uint64_t qhi, uint64_t qlo) {
+__device__ __forceinline__ uint32_t table_img_le(const OpenedSet& o, uint32_t nsst, uint32_t t, const KeyImage& qm) {
   if (t >= nsst) return 0;  // (the view check refuses such a view)
-  const u32x4 v = *reinterpret_cast<const u32x4*>(o.index + o.desc[t].blk0);
-  const uint64_t hi = (uint64_t(v.y) << 32) | v.x, lo = (uint64_t(v.w) << 32) | v.z;
-  return (hi < qhi || (hi == qhi && lo < qlo) ? 1u : 0u) | (hi < qhi || (hi == qhi && lo <= qlo) ? 2u : 0u);
+  const KeyImage v = KeyImage::pair(*reinterpret_cast<const u32x4*>(o.index + o.desc[t].blk0));
+  return (v < qm ? 1u : 0u) | (v <= qm ? 2u : 0u);
 }
 // ... and the partition point from the image bounds: whole keys inside [iL, iU)
 __device__ __forceinline__ uint32_t level_tie(const OpenedSet& o, uint32_t nsst, const uint32_t* ls, uint32_t iL, uint32_t iU,
@@ -841,38 +780,29 @@ __device__ __forceinline__ uint32_t level_tie(const OpenedSet& o, uint32_t nsst,
   return kary_first_false(iL, iU, [&](uint32_t i) {
     const uint32_t t = ls[i];
     if (t >= nsst) return false;
-    return lane_cmp(o.files + o.desc[t].first_key_pos, o.desc[t].first_key_len, q) <= 0;
+    return byte_cmp(KeyPtr{o.files + o.desc[t].first_key_pos, o.desc[t].first_key_len}, q) <= 0;
   });
 }
 __device__ __forceinline__ uint32_t level_partition(const OpenedSet& o, uint32_t nsst, const uint32_t* ls, uint32_t n,
-                                                    const QKey& q, uint64_t qhi, uint64_t qlo) {
-  const uint32_t iL = kary_first_false(0, n, [&](uint32_t i) { return (table_img_le(o, nsst, ls[i], qhi, qlo) & 1) != 0; });
-  const uint32_t iU = kary_first_false(iL, n, [&](uint32_t i) { return (table_img_le(o, nsst, ls[i], qhi, qlo) & 2) != 0; });
+                                                    const QKey& q, const KeyImage& qm) {
+  const uint32_t iL = kary_first_false(0, n, [&](uint32_t i) { return (table_img_le(o, nsst, ls[i], qm) & 1) != 0; });
+  const uint32_t iU = kary_first_false(iL, n, [&](uint32_t i) { return (table_img_le(o, nsst, ls[i], qm) & 2) != 0; });
   return level_tie(o, nsst, ls, iL, iU, q);
 }
 
-// Key order of file bytes p[0 .. len) against the query by one lane: their leading 16 bytes as
-// images (16 independent loads, one round trip) decide unless they tie.
-__device__ __forceinline__ int lane_cmp_img(const uint8_t* p, uint32_t len, const QKey& q, uint64_t qhi, uint64_t qlo) {
-  uint64_t hi = 0, lo = 0;
-#pragma unroll
-  for (uint32_t j = 0; j < 16; ++j) {
-    const uint64_t x = j < len ? p[j] : 0;
-    if (j < 8) hi |= x << (56 - 8 * j);
-    else lo |= x << (56 - 8 * (j - 8));
-  }
-  if (hi != qhi) return hi < qhi ? -1 : 1;
-  if (lo != qlo) return lo < qlo ? -1 : 1;
-  return lane_cmp(p, len, q);
+// Key order of file bytes p[0 .. len) against the query (image qm) by one lane: their leading 16
+// bytes as images (16 independent loads, one round trip) decide unless they tie.
+__device__ __forceinline__ int lane_cmp_img(const uint8_t* p, uint32_t len, const QKey& q, const KeyImage& qm) {
+  return image_byte_cmp(image_of_bytes(p, len), KeyPtr{p, len}, qm, q);
 }
 
 // keep_table (lsm_storage.rs:383-398) by one lane for its own table, in two steps so that the key
 // is hashed only when some table's range holds it: key_within ...
-__device__ __forceinline__ bool lane_key_within(const OpenedSet& o, uint32_t t, const QKey& q, uint64_t qhi, uint64_t qlo) {
+__device__ __forceinline__ bool lane_key_within(const OpenedSet& o, uint32_t t, const QKey& q, const KeyImage& qm) {
   const lsmblk_sst_desc* d = o.desc + t;
   if (d->nblk == 0) return false;  // not opened (the view check refuses such a view)
-  return lane_cmp_img(o.files + d->first_key_pos, d->first_key_len, q, qhi, qlo) <= 0 &&
-         lane_cmp_img(o.files + d->last_key_pos, d->last_key_len, q, qhi, qlo) >= 0;
+  return lane_cmp_img(o.files + d->first_key_pos, d->first_key_len, q, qm) <= 0 &&
+         lane_cmp_img(o.files + d->last_key_pos, d->last_key_len, q, qm) >= 0;
 }
 // ... and Bloom::may_contain (bloom.rs:104-120), every probe made (independent loads)
 __device__ __forceinline__ bool lane_may_contain(const OpenedSet& o, uint32_t t, uint32_t h) {
@@ -900,20 +830,9 @@ __device__ __forceinline__ MemArgs mem_keys(MemArgs m) {
 // the key's leading 16 bytes come from ONE 16-byte load at any alignment wherever 16 bytes from the
 // key's start lie inside the arena (every key but the last few) -- a probe is then three loads, not
 // eighteen -- and the bytes past the key's end are masked off.
-__device__ __forceinline__ int mem_cmp(const MemArgs& m, uint32_t i, const QKey& q, uint64_t qhi, uint64_t qlo) {
+__device__ __forceinline__ int mem_cmp(const MemArgs& m, uint32_t i, const QKey& q, const KeyImage& qm) {
   const uint32_t k0 = m.key_off[i], len = m.key_off[i + 1] - k0;
-  const uint8_t* p = m.keys + k0;
-  if (uint64_t(k0) + 16 > m.key_bytes) return lane_cmp_img(p, len, q, qhi, qlo);
-  const u32x4 v = *reinterpret_cast<const u32x4*>(p);
-  uint64_t hi = (uint64_t(__builtin_bswap32(v.x)) << 32) | __builtin_bswap32(v.y);
-  uint64_t lo = (uint64_t(__builtin_bswap32(v.z)) << 32) | __builtin_bswap32(v.w);
-  if (len < 16) {  // (len >= 1 for a run that obeys the precondition; 0 keeps nothing)
-    hi = len >= 8 ? hi : (len ? hi & (~0ull << (8 * (8 - len))) : 0ull);
-    lo = len > 8 ? lo & (~0ull << (8 * (16 - len))) : 0ull;
-  }
-  if (hi != qhi) return hi < qhi ? -1 : 1;
-  if (lo != qlo) return lo < qlo ? -1 : 1;
-  return lane_cmp(p, len, q);
+  return image_byte_cmp(image_of_load16(m.keys, m.key_bytes, k0, len), KeyPtr{m.keys + k0, len}, qm, q);
 }
 
 // The wave's lanes over the memtable runs: the 64 lanes are split evenly into lane groups of g = 2^lg
@@ -969,13 +888,13 @@ struct MemLook {
   uint32_t vlen;
   uint64_t ts;
 };
-__device__ __forceinline__ MemLook mem_lookup(const MemArgs& m, const MemGroups& G, const QKey& q, uint64_t qhi, uint64_t qlo,
+__device__ __forceinline__ MemLook mem_lookup(const MemArgs& m, const MemGroups& G, const QKey& q, const KeyImage& qm,
                                               uint64_t read_ts) {
   MemLook o{false, kNone, 0, 0};
   const uint32_t lo = G.on ? m.start[G.run] : 0u, end = G.on ? m.start[G.run + 1] : 0u;
-  const uint32_t land = group_first_false(G, lo, end, G.on, [&](uint32_t i) { return mem_cmp(m, i, q, qhi, qlo) < 0; });
+  const uint32_t land = group_first_false(G, lo, end, G.on, [&](uint32_t i) { return mem_cmp(m, i, q, qm) < 0; });
   if (G.lead()) {
-    for (uint32_t e = land; e < end && mem_cmp(m, e, q, qhi, qlo) == 0; ++e) {
+    for (uint32_t e = land; e < end && mem_cmp(m, e, q, qm) == 0; ++e) {
       o.on_key = true;
       const uint64_t t = m.ts[e];
       if (t <= read_ts) {
@@ -1015,8 +934,6 @@ __global__ __launch_bounds__(64 * kGetWaves) __attribute__((amdgpu_waves_per_eu(
   const uint32_t l = lane_id();
   uint8_t* const S = img[wave_id()];
   const bool newest = (a.flags & LSMBLK_LSM_GET_NEWEST) != 0, mvcc = newest || (a.flags & LSMBLK_GET_MVCC) != 0;
-  const uint32_t qlead = uint32_t(reinterpret_cast<uintptr_t>(a.qkeys) & 3);
-  const uint8_t* const qbase = a.qkeys - qlead;
   const OpenedSet& o = a;
   const bool run = uni(*a.vflag) == 0;
   const uint32_t nsrc = a.nl0 + a.nlevel;
@@ -1033,13 +950,12 @@ __global__ __launch_bounds__(64 * kGetWaves) __attribute__((amdgpu_waves_per_eu(
     const uint32_t k0 = uni(a.qkey_off[qi]), k1 = uni(a.qkey_off[qi + 1]);
     if (run && k1 <= k0) err |= LSMBLK_ERR_EMPTY_KEY;
     if (run && k1 > k0) {
-      const QKey q{make_rsrc_exact(const_cast<uint8_t*>(qbase), (qlead + k1 + 3) & ~3u), qlead + k0, k1 - k0};
+      const QKey q = key_upto(a.qkeys, k0, k1);
       const uint64_t read_ts = uni64(a.q_ts[qi]);
-      uint64_t qhi, qlo;
-      query_image(q, qhi, qlo);
+      const KeyImage qm = image_of(q);
       uint64_t ltm = 0, lem = 0;  // nlv <= 64: level table i's image below / not above the query's
       if (nlv && nlv <= 64) {
-        const uint32_t c = l < nlv ? table_img_le(o, a.nsst, a.level_sst[l], qhi, qlo) : 0u;
+        const uint32_t c = l < nlv ? table_img_le(o, a.nsst, a.level_sst[l], qm) : 0u;
         ltm = __ballot((c & 1) != 0);
         lem = __ballot((c & 2) != 0);
       }
@@ -1047,7 +963,7 @@ __global__ __launch_bounds__(64 * kGetWaves) __attribute__((amdgpu_waves_per_eu(
       if constexpr (kMem) {
         const MemArgs mem = mem_keys(a.mem);
         const MemGroups G = mem_groups(mem.nmem);
-        const MemLook ml = mem_lookup(mem, G, q, qhi, qlo, read_ts);
+        const MemLook ml = mem_lookup(mem, G, q, qm, read_ts);
         // (a run's result is in its group's first lane: lane order is ordinal order)
         const uint64_t onm = __ballot(ml.on_key), hitm = __ballot(ml.hit != kNone);
         uint32_t w = kNone;  // the lane that answers
@@ -1094,14 +1010,14 @@ __global__ __launch_bounds__(64 * kGetWaves) __attribute__((amdgpu_waves_per_eu(
             P = level_tie(o, a.nsst, a.level_sst + lo, uint32_t(__builtin_popcountll(ltm & m)),
                           uint32_t(__builtin_popcountll(lem & m)), q);
           } else {
-            P = level_partition(o, a.nsst, a.level_sst + lo, hi - lo, q, qhi, qlo);
+            P = level_partition(o, a.nsst, a.level_sst + lo, hi - lo, q, qm);
           }
           if (P == 0) continue;    // below the level's first table
           const uint32_t t = uni(a.level_sst[lo + P - 1]);
           if (l == src - base) myt = t;
         }
         // (a key above the table's last key: a gap of the level, or past it)
-        const bool within = myt < a.nsst && lane_key_within(o, myt, q, qhi, qlo);
+        const bool within = myt < a.nsst && lane_key_within(o, myt, q, qm);
         bool pass = false;
         if (__ballot(within)) {
           if (!qh.valid) {
@@ -1297,8 +1213,6 @@ __global__ __launch_bounds__(64 * kGetWaves) void scan_bounds_kernel(ScanArgs a)
   const uint32_t l = lane_id();
   uint8_t* const S = img[wave_id()];
   const bool mvcc = (a.flags & LSMBLK_SCAN_MVCC) != 0, filter = !(a.flags & LSMBLK_SCAN_NO_FILTER);
-  const uint32_t llead = uint32_t(reinterpret_cast<uintptr_t>(a.lkeys) & 3);
-  const uint32_t ulead = uint32_t(reinterpret_cast<uintptr_t>(a.ukeys) & 3);
   uint32_t err = 0;
   const uint64_t stride = uint64_t(gridDim.x) * kGetWaves;
   const uint64_t nq = scan_nq<kSub>(a);
@@ -1333,8 +1247,7 @@ __global__ __launch_bounds__(64 * kGetWaves) void scan_bounds_kernel(ScanArgs a)
         break;
       }
       // (an unbounded side: an empty descriptor, never read)
-      const QKey lo{make_rsrc_exact(const_cast<uint8_t*>(a.lkeys - llead), lk ? (llead + l1 + 3) & ~3u : 0u), llead + l0, l1 - l0};
-      const QKey up{make_rsrc_exact(const_cast<uint8_t*>(a.ukeys - ulead), uk ? (ulead + u1 + 3) & ~3u : 0u), ulead + u0, u1 - u0};
+      const QKey lo = key_upto(a.lkeys, l0, l1), up = key_upto(a.ukeys, u0, u1);
       const lsmblk_sst_desc* dp = a.desc + s;
       const uint32_t nblk = uni(dp->nblk), mo = uni(dp->meta_offset);
       if (nblk == 0) break;  // not opened
@@ -1797,22 +1710,6 @@ struct LsmScanArgs : OpenedSet, ViewArgs, BoundArgs {
   uint64_t slot_cap;
 };
 
-// Order of raw key x[0 .. lx) against the lane's own key y[0 .. ly), whose image is (yhi, ylo): the
-// leading 16 bytes as images (independent loads, one round trip) decide unless they tie.
-__device__ __forceinline__ int lane_cmp_img2(const uint8_t* x, uint32_t lx, const uint8_t* y, uint32_t ly, uint64_t yhi,
-                                             uint64_t ylo) {
-  uint64_t hi = 0, lo = 0;
-#pragma unroll
-  for (uint32_t j = 0; j < 16; ++j) {
-    const uint64_t b = j < lx ? x[j] : 0;
-    if (j < 8) hi |= b << (56 - 8 * j);
-    else lo |= b << (56 - 8 * (j - 8));
-  }
-  if (hi != yhi) return hi < yhi ? -1 : 1;
-  if (lo != ylo) return lo < ylo ? -1 : 1;
-  return lane_cmp2(x, lx, y, ly);
-}
-
 // One wave per range, grid-strided, over the view's tables in priority order; every candidate table
 // is tested by its own lane with range_overlap (lsm_storage.rs:142-167) against the descriptor's
 // first and last key.  A level's tables are ordered and disjoint (the view check), so the tables
@@ -1827,8 +1724,6 @@ __global__ __launch_bounds__(64 * kGetWaves) void lsm_scan_expand_kernel(LsmScan
     if (uni64(a.nsub[0]) == 0) return;
   }
   const bool run = uni(*a.vflag) == 0;
-  const uint32_t llead = uint32_t(reinterpret_cast<uintptr_t>(a.lkeys) & 3);
-  const uint32_t ulead = uint32_t(reinterpret_cast<uintptr_t>(a.ukeys) & 3);
   uint32_t err = 0;
   const uint64_t stride = uint64_t(gridDim.x) * kGetWaves;
   for (uint64_t qi = uint64_t(blockIdx.x) * kGetWaves + wave_id(); qi < a.nq; qi += stride) {
@@ -1855,20 +1750,19 @@ __global__ __launch_bounds__(64 * kGetWaves) void lsm_scan_expand_kernel(LsmScan
         err |= LSMBLK_ERR_EMPTY_KEY;
         break;
       }
-      const QKey lo{make_rsrc_exact(const_cast<uint8_t*>(a.lkeys - llead), lk ? (llead + l1 + 3) & ~3u : 0u), llead + l0, l1 - l0};
-      const QKey up{make_rsrc_exact(const_cast<uint8_t*>(a.ukeys - ulead), uk ? (ulead + u1 + 3) & ~3u : 0u), ulead + u0, u1 - u0};
-      uint64_t lhi = 0, llo = 0, uhi = 0, ulo = 0;
-      if (lk) query_image(lo, lhi, llo);
-      if (uk) query_image(up, uhi, ulo);
+      const QKey lo = key_upto(a.lkeys, l0, l1), up = key_upto(a.ukeys, u0, u1);
+      KeyImage lm{0, 0}, um{0, 0};
+      if (lk) lm = image_of(lo);
+      if (uk) um = image_of(up);
       // table t's first key against the upper bound, its last key against the lower bound
       auto first_in = [&](uint32_t t) {
         const lsmblk_sst_desc* d = a.desc + t;
-        const int c = lane_cmp_img(a.files + d->first_key_pos, d->first_key_len, up, uhi, ulo);
+        const int c = lane_cmp_img(a.files + d->first_key_pos, d->first_key_len, up, um);
         return uk == LSMBLK_BOUND_EXCLUDED ? c < 0 : c <= 0;
       };
       auto last_before = [&](uint32_t t) {
         const lsmblk_sst_desc* d = a.desc + t;
-        const int c = lane_cmp_img(a.files + d->last_key_pos, d->last_key_len, lo, lhi, llo);
+        const int c = lane_cmp_img(a.files + d->last_key_pos, d->last_key_len, lo, lm);
         return lk == LSMBLK_BOUND_EXCLUDED ? c <= 0 : c < 0;
       };
       // ids[i0 .. i1): each tested by its own lane, the passing ones taken in order
@@ -1901,11 +1795,11 @@ __global__ __launch_bounds__(64 * kGetWaves) void lsm_scan_expand_kernel(LsmScan
           x1 = a.mem.start[G.run + 1];
           ok = x1 > x0;
           if (ok && uk) {
-            const int c = mem_cmp(mem, x0, up, uhi, ulo);
+            const int c = mem_cmp(mem, x0, up, um);
             ok = uk == LSMBLK_BOUND_EXCLUDED ? c < 0 : c <= 0;
           }
           if (ok && lk) {
-            const int c = mem_cmp(mem, x1 - 1, lo, lhi, llo);
+            const int c = mem_cmp(mem, x1 - 1, lo, lm);
             ok = !(lk == LSMBLK_BOUND_EXCLUDED ? c <= 0 : c < 0);
           }
         }
@@ -1921,12 +1815,12 @@ __global__ __launch_bounds__(64 * kGetWaves) void lsm_scan_expand_kernel(LsmScan
           uint32_t b = x0, e = x1;
           if (lk)
             b = group_first_false(G, x0, x1, on, [&](uint32_t i) {
-              const int c = mem_cmp(mem, i, lo, lhi, llo);
+              const int c = mem_cmp(mem, i, lo, lm);
               return excl ? c <= 0 : c < 0;
             });
           if (uk)
             e = group_first_false(G, b, x1, on, [&](uint32_t i) {
-              const int c = mem_cmp(mem, i, up, uhi, ulo);
+              const int c = mem_cmp(mem, i, up, um);
               return strict ? c < 0 : c <= 0;
             });
           if (on && G.sub == 0) {
@@ -2026,19 +1920,18 @@ __global__ __launch_bounds__(256) void lsm_scan_rank_kernel(LsmScanArgs a) {
       const uint32_t r0 = a.sbase[q], r1 = a.sbase[q + 1];
       const uint8_t* const kp = a.raw.keys + a.raw.key_off[e];
       const uint32_t kl = klen(e);
-      uint64_t khi = 0, klo = 0;
-#pragma unroll
-      for (uint32_t j = 0; j < 16; ++j) {
-        const uint64_t b = j < kl ? kp[j] : 0;
-        if (j < 8) khi |= b << (56 - 8 * j);
-        else klo |= b << (56 - 8 * (j - 8));
-      }
-      auto cmp_key = [&](uint64_t x) { return lane_cmp_img2(a.raw.keys + a.raw.key_off[x], klen(x), kp, kl, khi, klo); };
+      // raw key x against the lane's own: images first (independent loads, one round trip)
+      const KeyImage km = image_of_bytes(kp, kl);
+      auto cmp_key = [&](uint64_t x) {
+        const uint8_t* const xp = a.raw.keys + a.raw.key_off[x];
+        const uint32_t xl = klen(x);
+        return image_byte_cmp(image_of_bytes(xp, xl), KeyPtr{xp, xl}, km, KeyPtr{kp, kl});
+      };
       // the reader's rule on e and its own run's predecessor
       auto own_rule = [&](uint64_t read_ts) {
         bool k = a.raw.ts[e] <= read_ts && a.raw.val_off[e + 1] > a.raw.val_off[e];
         if (k && e > a.sseg[r] && a.raw.ts[e - 1] <= read_ts)
-          k = lane_cmp2(a.raw.keys + a.raw.key_off[e - 1], klen(e - 1), kp, kl) != 0;
+          k = byte_cmp(KeyPtr{a.raw.keys + a.raw.key_off[e - 1], klen(e - 1)}, KeyPtr{kp, kl}) != 0;
         return k;
       };
       uint64_t ets = 0, snap_ts = 0;

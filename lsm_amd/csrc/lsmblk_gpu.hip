@@ -1416,45 +1416,7 @@ constexpr uint32_t kAlcpUnsorted = 0x80000000u;
 constexpr uint32_t kAlcpLcp = 0x7FFFFFFFu;
 
 // Key bytes of the batch through one descriptor over the whole key arena.
-struct PlanKeys {
-  rsrc_t gk;       // whole key arena, base aligned down to 16
-  uint32_t glead;  // keys pointer & 15
-  __device__ __forceinline__ uint32_t dword(uint32_t pos) const {  // 4 bytes at arena pos
-    const uint32_t x = glead + pos, al = x & ~3u;
-    const uint32_t w0 = __builtin_amdgcn_raw_buffer_load_b32(gk, al, 0, 0);
-    const uint32_t w1 = __builtin_amdgcn_raw_buffer_load_b32(gk, al + 4, 0, 0);
-    return __builtin_amdgcn_alignbyte(w1, w0, x & 3);
-  }
-};
-
-__device__ __forceinline__ PlanKeys plan_keys(const PlanArgs& a) {
-  PlanKeys K;
-  K.glead = uint32_t(reinterpret_cast<uintptr_t>(a.keys) & 15);
-  K.gk = make_rsrc(a.keys - K.glead, K.glead + uni(a.key_off[a.n]));
-  return K;
-}
-
-// LCP of keys (pp, pl) and (kp, kl); *w0 / *w1 = the dwords holding the first difference.
-__device__ __forceinline__ uint32_t key_lcp(const PlanKeys& K, uint32_t pp, uint32_t pl, uint32_t kp, uint32_t kl,
-                                            uint32_t& w0, uint32_t& w1) {
-  const uint32_t m = pl < kl ? pl : kl;
-  uint32_t lcp = m;
-  w0 = w1 = 0;
-  for (uint32_t d = 0; 4 * d < m; ++d) {
-    const uint32_t x0 = K.dword(pp + 4 * d), x1 = K.dword(kp + 4 * d);
-    if (x0 != x1) {
-      const uint32_t z = 4 * d + (__builtin_ctz(x0 ^ x1) >> 3);
-      if (z < m) {
-        lcp = z;
-        w0 = x0;
-        w1 = x1;
-      }
-      break;
-    }
-  }
-  return lcp;
-}
-
+__device__ __forceinline__ ArenaKeys plan_keys(const PlanArgs& a) { return ArenaKeys(a.keys, uni(a.key_off[a.n])); }
 
 constexpr uint32_t kWalkThreads = 512;  // 4 walker waves + their 4 helper (producer) waves
 constexpr uint32_t kSpinMax = 1u << 24;  // LDS hand-off polls before a wave gives up (TIMEOUT)
@@ -1469,12 +1431,12 @@ constexpr uint32_t kChunk = 256;         // entries per producer hand-off (1024 
 // written chunk by chunk into the walker's ring (slot (e - s0) % kRing), never to HBM.
 // A chunk may overwrite the ring's older half once the walker's window has left it;
 // prod[0] = entries produced (relative to s0), cons[0] = walker's window start (relative).
-__device__ void plan_produce(const PlanArgs& a, const PlanKeys& K, uint32_t s0, uint32_t s1, uint32_t* CR,
+__device__ void plan_produce(const PlanArgs& a, const ArenaKeys& K, uint32_t s0, uint32_t s1, uint32_t* CR,
                              uint32_t* CA, uint32_t* prod, const uint32_t* cons, uint32_t& err, uint64_t* tr) {
   const uint32_t l = lane_id();
   uint64_t waited = 0;
   if (tr && l == 0) tr[4] = __builtin_amdgcn_s_memrealtime();
-  const uint32_t klim = K.glead + uni(a.key_off[a.n]);
+  const uint32_t klim = K.lead + uni(a.key_off[a.n]);
   for (uint32_t c = s0; c < s1; c += kChunk) {
     const uint32_t cend = s1 - c < kChunk ? s1 : c + kChunk;
     if (c - s0 + kChunk > kRing) {  // ring space: the walker's window must have passed c + kChunk - kRing
@@ -1512,8 +1474,8 @@ __device__ void plan_produce(const PlanArgs& a, const PlanKeys& K, uint32_t s0, 
       for (uint32_t i = 0; i < kProdBatch; ++i) {
         const uint32_t e = c + 64 * (h + i) + l;
         if (e < cend && e != s0 && !nokeys) {
-          xk[i] = __builtin_amdgcn_raw_buffer_load_b128(K.gk, K.glead + kp[i], 0, 0);
-          xp[i] = __builtin_amdgcn_raw_buffer_load_b128(K.gk, K.glead + pp[i], 0, 0);
+          xk[i] = __builtin_amdgcn_raw_buffer_load_b128(K.r, K.lead + kp[i], 0, 0);
+          xp[i] = __builtin_amdgcn_raw_buffer_load_b128(K.r, K.lead + pp[i], 0, 0);
         }
       }
 #pragma unroll
@@ -1531,7 +1493,7 @@ __device__ void plan_produce(const PlanArgs& a, const PlanKeys& K, uint32_t s0, 
           const uint32_t pl = kp[i] - pp[i], m = pl < kl ? pl : kl;
           uint32_t lcp = m, w0 = 0, w1 = 0;
           bool done = false;
-          if (K.glead + kp[i] + 16 <= klim && K.glead + pp[i] + 16 <= klim) {
+          if (K.lead + kp[i] + 16 <= klim && K.lead + pp[i] + 16 <= klim) {
             // first differing byte z of the 16 loaded (16: none), by selects instead of a branch per
             // dword (the helper shares its SIMD with the walker: its instructions are the walk's time)
             const uint32_t P[4] = {xp[i].x, xp[i].y, xp[i].z, xp[i].w}, Q[4] = {xk[i].x, xk[i].y, xk[i].z, xk[i].w};
@@ -1548,7 +1510,7 @@ __device__ void plan_produce(const PlanArgs& a, const PlanKeys& K, uint32_t s0, 
             done = z16 < m || m <= 16;
             if (!done) {  // equal first 16 bytes: the rest by dwords
               for (uint32_t d = 4; 4 * d < m; ++d) {
-                const uint32_t y0 = K.dword(pp[i] + 4 * d), y1 = K.dword(kp[i] + 4 * d);
+                const uint32_t y0 = K.dw(pp[i] + 4 * d), y1 = K.dw(kp[i] + 4 * d);
                 if (y0 != y1) {
                   const uint32_t z = 4 * d + (__builtin_ctz(y0 ^ y1) >> 3);
                   if (z < m) {
@@ -1561,7 +1523,8 @@ __device__ void plan_produce(const PlanArgs& a, const PlanKeys& K, uint32_t s0, 
               }
             }
           } else {
-            lcp = key_lcp(K, pp[i], pl, kp[i], kl, w0, w1);
+            const KeyDiff kd = key_diff(K, pp[i], pl, kp[i], kl);
+            lcp = kd.lcp, w0 = kd.w0, w1 = kd.w1;
           }
           const uint32_t sh = 8 * (lcp & 3);
           const bool sorted = lcp == m ? pl <= kl : ((w0 >> sh) & 0xFF) < ((w1 >> sh) & 0xFF);
@@ -1596,7 +1559,7 @@ struct WalkRing {
 // order, goes to sink(first entry, end entry, encoded size, blocks before it in the segment,
 // bytes before it in the segment) (wave-uniform arguments); returns (blocks, bytes).
 template <class Sink>
-__device__ __forceinline__ void walk_segment(const PlanArgs& a, const PlanKeys& K, WalkRing& R, uint32_t s0, uint32_t s1,
+__device__ __forceinline__ void walk_segment(const PlanArgs& a, const ArenaKeys& K, WalkRing& R, uint32_t s0, uint32_t s1,
                                              uint32_t& err, uint32_t& nb, uint64_t& bytes, Sink&& sink, uint64_t* tr,
                                              uint64_t& waited, uint64_t& windows) {
   const uint32_t l = lane_id();
@@ -1701,8 +1664,7 @@ __device__ __forceinline__ void walk_segment(const PlanArgs& a, const PlanKeys& 
         pmin = __builtin_amdgcn_readlane(p, 63);
       } else if (valid && e != s) {
         const uint32_t kp = a.key_off[e], kl = a.key_off[e + 1] >= kp ? a.key_off[e + 1] - kp : 0u;
-        uint32_t w0, w1;
-        p = key_lcp(K, sp, sl, kp, kl, w0, w1);
+        p = key_diff(K, sp, sl, kp, kl).lcp;
       }
       if (e == s) p = 0;
       // data growth + offset slot, its inclusive scan and estimated_size() before adding e.  u32
@@ -1811,12 +1773,12 @@ __device__ __forceinline__ void prod_offs_land(ProdOffs& P) {
   for (uint32_t i = 0; i < kPipeB; ++i)
     asm volatile("" : "+v"(P.kp[i]), "+v"(P.kn[i]), "+v"(P.pp[i]), "+v"(P.v0[i]), "+v"(P.v1[i]));
 }
-__device__ void plan_produce_pipe(const PlanArgs& a, const PlanKeys& K, uint32_t s0, uint32_t s1, uint32_t* CR,
+__device__ void plan_produce_pipe(const PlanArgs& a, const ArenaKeys& K, uint32_t s0, uint32_t s1, uint32_t* CR,
                                   uint32_t* CA, uint32_t* prod, const uint32_t* cons, uint32_t& err,
                                   uint64_t* tr = nullptr) {
   static_assert(kPipeB == 2, "the vmcnt below counts 5 kPipeB offset loads");
   const uint32_t l = lane_id();
-  const uint32_t klim = K.glead + uni(a.key_off[a.n]);
+  const uint32_t klim = K.lead + uni(a.key_off[a.n]);
   uint64_t waited = 0;
   if (tr && l == 0) tr[4] = __builtin_amdgcn_s_memrealtime();
   if (s0 >= s1) return;
@@ -1845,12 +1807,12 @@ __device__ void plan_produce_pipe(const PlanArgs& a, const PlanKeys& K, uint32_t
     u32x4 xk[kPipeB], xp[kPipeB];
 #pragma unroll
     for (uint32_t i = 0; i < kPipeB; ++i) {
-      const uint32_t ok = K.glead + P.kp[i], op = K.glead + P.pp[i];
+      const uint32_t ok = K.lead + P.kp[i], op = K.lead + P.pp[i];
       asm volatile(
           "buffer_load_dwordx4 %0, %2, %4, 0 offen\n\t"
           "buffer_load_dwordx4 %1, %3, %4, 0 offen"
           : "=&v"(xk[i]), "=&v"(xp[i])
-          : "v"(ok), "v"(op), "s"(K.gk));
+          : "v"(ok), "v"(op), "s"(K.r));
     }
     // the next batch's offsets (after the last batch: its own again -- always 5 kPipeB loads)
     const uint32_t cn = c + kPipeE < s1 ? c + kPipeE : c;
@@ -1871,7 +1833,7 @@ __device__ void plan_produce_pipe(const PlanArgs& a, const PlanKeys& K, uint32_t
       if (e != s0) {  // LCP with the predecessor, bit 31 = out of order (as plan_produce)
         const uint32_t pl = kp - pp, m = pl < kl ? pl : kl;
         uint32_t lcp = m, w0 = 0, w1 = 0;
-        if (K.glead + kp + 16 <= klim && K.glead + pp + 16 <= klim) {
+        if (K.lead + kp + 16 <= klim && K.lead + pp + 16 <= klim) {
           const uint32_t Pw[4] = {xp[i].x, xp[i].y, xp[i].z, xp[i].w}, Qw[4] = {xk[i].x, xk[i].y, xk[i].z, xk[i].w};
           uint32_t t[4];
 #pragma unroll
@@ -1885,7 +1847,7 @@ __device__ void plan_produce_pipe(const PlanArgs& a, const PlanKeys& K, uint32_t
           }
           if (!(z16 < m || m <= 16)) {  // equal first 16 bytes: the rest by dwords
             for (uint32_t d = 4; 4 * d < m; ++d) {
-              const uint32_t y0 = K.dword(pp + 4 * d), y1 = K.dword(kp + 4 * d);
+              const uint32_t y0 = K.dw(pp + 4 * d), y1 = K.dw(kp + 4 * d);
               if (y0 != y1) {
                 const uint32_t z = 4 * d + (__builtin_ctz(y0 ^ y1) >> 3);
                 if (z < m) {
@@ -1898,7 +1860,8 @@ __device__ void plan_produce_pipe(const PlanArgs& a, const PlanKeys& K, uint32_t
             }
           }
         } else {
-          lcp = key_lcp(K, pp, pl, kp, kl, w0, w1);
+          const KeyDiff kd = key_diff(K, pp, pl, kp, kl);
+          lcp = kd.lcp, w0 = kd.w0, w1 = kd.w1;
         }
         const uint32_t sh = 8 * (lcp & 3);
         const bool sorted = lcp == m ? pl <= kl : ((w0 >> sh) & 0xFF) < ((w1 >> sh) & 0xFF);
@@ -1948,7 +1911,7 @@ __global__ __launch_bounds__(kWalkThreads) __attribute__((amdgpu_waves_per_eu(4)
     s1 = s0 = (s0 > a.n ? uint32_t(a.n) : s0);
     if (s1 < s0) s1 = s0;
   }
-  const PlanKeys K = plan_keys(a);
+  const ArenaKeys K = plan_keys(a);
   uint64_t* const tr = kDiag && a.dbg && g < kDbgTiles ? a.dbg + 16 + 8 * uint64_t(g) : nullptr;  // (diagnostics)
   if (wv >= 4) {
     if (a.pipe_helper) plan_produce_pipe(a, K, s0, s1, CR, CA, &hand_prod[ww], &hand_cons[ww], err, tr);
@@ -2913,7 +2876,7 @@ __device__ void fuse_walk(const FuseArgs& f, uint32_t* ring) {
     if ((g == 0 && s0 != 0) || (g == a.nseg - 1 && uint64_t(s1) != a.n) || s0 > s1 || uint64_t(s1) > a.n) ok = false;
   }
   const uint32_t S0 = ok ? uni(a.seg_start[g0]) : 0u, S1 = ok ? uni(a.seg_start[g1]) : 0u;
-  const PlanKeys K = plan_keys(a);
+  const ArenaKeys K = plan_keys(a);
   if (wv >= 2) {
     plan_produce_pipe(a, K, S0, S1, CR, CA, prod, cons, err);
     const uint32_t werr = (__ballot(err & LSMBLK_ERR_EMPTY_KEY) ? LSMBLK_ERR_EMPTY_KEY : 0u) |
@@ -3923,28 +3886,11 @@ __device__ __forceinline__ bool filt_keep(const FiltArgs& a, uint64_t i) {
   bool start = true;
   if (i > 0) {
     const uint32_t p0 = a.key_off[i - 1];
-    const uint32_t kl = k1 - k0;
-    if (k0 - p0 == kl) {
-      start = false;
-      uint32_t j = 0;
-      for (; j + 16 <= kl && !start; j += 16) {  // unaligned 16-B compares, then bytes
-        const u32x4 x = *reinterpret_cast<const u32x4*>(a.keys + p0 + j);
-        const u32x4 y = *reinterpret_cast<const u32x4*>(a.keys + k0 + j);
-        start = x.x != y.x || x.y != y.y || x.z != y.z || x.w != y.w;
-      }
-      for (; j < kl && !start; ++j) start = a.keys[p0 + j] != a.keys[k0 + j];
-    }
+    start = !key_equal(KeyPtr{a.keys + p0, k0 - p0}, KeyPtr{a.keys + k0, k1 - k0});
     if (!start && a.ts[i - 1] <= a.wm) return false;  // a later version below the watermark
   }
   if (a.bottom && start && a.val_off[i + 1] == a.val_off[i]) return false;
-  for (uint32_t f = 0; f < a.npfx; ++f) {
-    const uint32_t f0 = a.pfx_off[f], fl = a.pfx_off[f + 1] - f0;
-    if (fl > k1 - k0) continue;
-    bool m = true;
-    for (uint32_t j = 0; j < fl && m; ++j) m = a.pfx[f0 + j] == a.keys[k0 + j];
-    if (m) return false;
-  }
-  return true;
+  return !has_any_prefix(KeyPtr{a.keys + k0, k1 - k0}, a.pfx, a.pfx_off, a.npfx);
 }
 
 __global__ __launch_bounds__(256) void filt_flag_kernel(FiltArgs a) {
@@ -4071,16 +4017,7 @@ __device__ __forceinline__ bool readf_keep(const ReadFiltArgs& a, uint64_t i) {
   if (f.ts[i] > T || f.val_off[i + 1] == f.val_off[i]) return false;
   if (i == 0 || i == a.seg_start[lo] || f.ts[i - 1] > T) return true;  // nothing is compared across a segment start
   const uint32_t k0 = f.key_off[i], kl = f.key_off[i + 1] - k0, p0 = f.key_off[i - 1];
-  if (k0 - p0 != kl) return true;
-  bool differ = false;
-  uint32_t j = 0;
-  for (; j + 16 <= kl && !differ; j += 16) {  // unaligned 16-B compares, then bytes
-    const u32x4 x = *reinterpret_cast<const u32x4*>(f.keys + p0 + j);
-    const u32x4 y = *reinterpret_cast<const u32x4*>(f.keys + k0 + j);
-    differ = x.x != y.x || x.y != y.y || x.z != y.z || x.w != y.w;
-  }
-  for (; j < kl && !differ; ++j) differ = f.keys[p0 + j] != f.keys[k0 + j];
-  return differ;
+  return !key_equal(KeyPtr{f.keys + p0, k0 - p0}, KeyPtr{f.keys + k0, kl});
 }
 
 __global__ __launch_bounds__(256) void readf_flag_kernel(ReadFiltArgs a) {
@@ -4900,4 +4837,4 @@ int launch_crc_frames(lsmblk_ctx* c, uint8_t* out, const uint64_t* blk_off, cons
   b.dnblk = stats;
   return launch_crc_stream(c, b, nblk_max, st);
 }
-}  // namespace lsmblk_impl lsmblk_impl
+}  // namespace lsmblk_impl

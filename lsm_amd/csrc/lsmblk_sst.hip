@@ -23,27 +23,8 @@
 
 namespace {
 
-// (farmhash fingerprint32 and wave_copy_bytes live in lsmblk_dev.hpp: lsmblk_get.hip shares them)
-// A key in the KV stream's arena through a bounds-checked descriptor (aligned dword loads).
-struct DevKey {
-  rsrc_t r;
-  uint32_t x;  // descriptor byte of the key's first byte
-  __device__ __forceinline__ uint32_t fetch(uint32_t i) const {
-    const uint32_t y = x + i, al = y & ~3u;
-    return __builtin_amdgcn_alignbyte(__builtin_amdgcn_raw_buffer_load_b32(r, al + 4, 0, 0),
-                                      __builtin_amdgcn_raw_buffer_load_b32(r, al, 0, 0), y & 3);
-  }
-  __device__ __forceinline__ uint32_t byte(uint32_t i) const { return __builtin_amdgcn_raw_buffer_load_b8(r, x + i, 0, 0); }
-};
-struct HostKey {
-  const uint8_t* p;
-  uint32_t fetch(uint32_t i) const {
-    uint32_t v;
-    memcpy(&v, p + i, 4);
-    return v;
-  }
-  uint32_t byte(uint32_t i) const { return p[i]; }
-};
+// (farmhash fingerprint32, its key sources and wave_copy_bytes live in lsmblk_dev.hpp: lsmblk_get.hip
+// shares them)
 
 // ---------------------------------------------------------------- bloom geometry
 // Bloom::bloom_bits_per_key(n, 0.01) (bloom.rs:72-77) in f64 as the reference computes it, then
@@ -213,14 +194,13 @@ __global__ __launch_bounds__(256) void sst_bloom_kernel(SstArgs a) {
     __threadfence();  // the zeros reach L2 before any thread's atomics
   }
   __syncthreads();
-  const uint32_t lead = uint32_t(reinterpret_cast<uintptr_t>(a.keys) & 15);
-  const rsrc_t R = make_rsrc(a.keys - lead, lead + a.key_off[a.n]);
+  const ArenaKeys K(a.keys, a.key_off[a.n]);
   // global path: OR into the file bytes through the aligned words that hold them
   uint8_t* const dal = reinterpret_cast<uint8_t*>(reinterpret_cast<uintptr_t>(d) & ~uintptr_t(3));
   const uint32_t dsh = uint32_t(reinterpret_cast<uintptr_t>(d) & 3);
   for (uint32_t e = e0 + threadIdx.x; e < e1; e += 256) {
     const uint32_t kp = a.key_off[e], kl = a.key_off[e + 1] - kp;
-    uint32_t h = fingerprint32(DevKey{R, lead + kp}, kl);
+    uint32_t h = fingerprint32(KeyRef<ArenaKeys>{K, kp, kl}, kl);
     const uint32_t delta = (h >> 17) | (h << 15);
     for (uint32_t i = 0; i < G.k; ++i) {
       const uint32_t bit = uint32_t(uint64_t(h) % G.nbits);
@@ -413,7 +393,7 @@ int lsmblk_seek_batch(lsmblk_ctx* c, const uint8_t* blocks, const uint64_t* blk_
 }
 
 uint32_t lsmblk_fingerprint32(const uint8_t* key, size_t klen) {
-  return fingerprint32(HostKey{key}, uint32_t(klen));
+  return fingerprint32(KeyRef<CpuKeys>{CpuKeys{key, uint32_t(klen)}, 0, uint32_t(klen)}, uint32_t(klen));
 }
 
 int lsmblk_bloom_may_contain(const uint8_t* filter, size_t nbytes, uint32_t k, uint32_t h) {

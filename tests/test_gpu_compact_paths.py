@@ -103,9 +103,9 @@ def rotation_raw(d, bs, target, sst_cap):
 @pytest.mark.parametrize("last", cc.KEY_ORDER_LAST)
 def test_key_order_through_the_16_byte_images(last):
     """Zero bytes, zero-extended prefixes, 16-byte keys beside longer ones, tails that first differ
-    at byte 1-5, 8, 9 (the partial-dword masks of key_cmp / glcp), a 65 535-byte key, and a long
+    at byte 1-5, 8, 9 (the partial last dword of key_diff), a 65 535-byte key, and a long
     last key of the arena: merge in both modes, the rules + rotation + blocks (rot_adj through
-    kidx / lcp_k16), and the stand-alone rotation of the kept stream (rot_adj through glcp)."""
+    kidx / image_lcp), and the stand-alone rotation of the kept stream (rot_adj through key_diff)."""
     case = cc.key_order(last)
     nkeys, nties = cc.check_key_order(case)
     merged = check_merge(case)
@@ -120,7 +120,7 @@ def test_key_order_through_the_16_byte_images(last):
 
 
 def test_lcp_of_zero_padded_images():
-    """lcp_k16 where the 16-byte images first differ past the shorter key's end (a zero pad against
+    """image_lcp where the 16-byte images first differ past the shorter key's end (a zero pad against
     zero bytes of the longer key): the LCP is the shorter length.  The first SST's end depends on it."""
     case = cc.pad_lcp()
     nsst = cc.check_pad_lcp(case)

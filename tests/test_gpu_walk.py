@@ -92,7 +92,7 @@ def test_pair_probes_every_route_and_alignment():
 
 def test_tail_probes_every_alignment():
     """Streams whose last keys are 1 to 15 bytes long: the pairs within 16 bytes of the arena's end
-    (key_lcp through alignbyte loads), sorted, unsorted and prefixes."""
+    (key_diff through alignbyte loads), sorted, unsorted and prefixes."""
     seen = {}
     for i, case in enumerate(wc.tail_probes()):
         P = rehomed_helpers(case, f"tail_probes[{i}]", seen)

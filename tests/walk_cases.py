@@ -7,7 +7,7 @@ which prefix every entry gets.  Shared by test_walk_cases.py (CPU) and test_gpu_
   constants    kRing, kChunk, kProdBatch, kPipeB, kAlcpLcp and the literals of walk_segment's
                narrow / 64-bit split, read out of the kernel source
   classify_pairs   per adjacent pair of keys inside a segment, what the helper computes (min length,
-               LCP, order) and the route it takes to it (16-byte select, dword loop, key_lcp tail)
+               LCP, order) and the route it takes to it (16-byte select, dword loop, key_diff tail)
   walk         a lane-level restatement of walk_segment over those pair values: 64-entry windows,
                ballot and first stop, the inner loop, the open carry, direct mode, the huge-entry
                restart, u32 against 64-bit arithmetic.  Its block table must equal the oracle's on
@@ -408,7 +408,7 @@ def pair_probes(seed=401):
 
 def tail_probes(seed=402):
     """<= 24 streams (three long keys, then the probe as a segment of its own) whose last two or three keys are 1 to 15 bytes long, so that the
-    last pairs start within 16 bytes of the arena's end (the key_lcp route): first differences at
+    last pairs start within 16 bytes of the arena's end (the key_diff route): first differences at
     z & 3 = 0..3 sorted and unsorted, and the three prefix kinds."""
     rng = np.random.default_rng(seed)
     lead = [b"\x00" * 24, b"\x00" * 24 + b"\x05", b"\x00\x01" * 9]  # below every probe's first key
