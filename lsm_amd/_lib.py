@@ -3,6 +3,7 @@
 The library is built in-tree by lsm_amd/_build.py (``__graft_entry__.build()``).  There is
 no fallback: if the library is missing or fails to load, every call raises.
 """
+import contextlib
 import ctypes
 import os
 
@@ -26,7 +27,6 @@ LSMBLK_E_CHECKSUM = -9
 LSMBLK_DECODE_VERIFY_CRC = 1
 LSMBLK_ENCODE_SEG_SLOTS = 1
 LSMBLK_ENCODE_FRAMED = 2
-LSMBLK_DEBUG_ENCODE_FUSED = 8
 LSMBLK_SHARD_LAST = 1
 LSMBLK_MERGE_RUNS = 0
 LSMBLK_MERGE_TWO_LEVEL = 1
@@ -52,6 +52,27 @@ LSMBLK_SCAN_NO_FILTER = 1
 LSMBLK_SCAN_MVCC = 2
 LSMBLK_LSM_SCAN_NEWEST = 4
 LSMBLK_LSM_SCAN_STATS_WORDS = 8
+# stats[3] error flags
+LSMBLK_ERR_MALFORMED = 1
+LSMBLK_ERR_CAPACITY = 2
+LSMBLK_ERR_OVERFLOW = 4
+LSMBLK_ERR_TIMEOUT = 8
+LSMBLK_ERR_SEGMENTS = 16
+LSMBLK_ERR_INTERNAL = 32
+LSMBLK_ERR_EMPTY_KEY = 64
+LSMBLK_ERR_CHECKSUM = 128
+# lsmblk_debug_set keys
+LSMBLK_DEBUG_POLL_MODE = 0
+LSMBLK_DEBUG_DECODE_SKIP = 1
+LSMBLK_DEBUG_KERNEL_TIMING = 2
+LSMBLK_DEBUG_TWO_PASS_DECODE = 3
+LSMBLK_DEBUG_DECODE_LAG = 4
+LSMBLK_DEBUG_COUNTERS = 5
+LSMBLK_DEBUG_DECODE_LAG_BYTES = 6
+LSMBLK_DEBUG_ROT_POISON = 7
+LSMBLK_DEBUG_ENCODE_FUSED = 8
+LSMBLK_DEBUG_PLAN_PIPE = 9
+LSMBLK_DEBUG_EMIT_POISON = 10
 LSMBLK_DEBUG_SCAN_UNITS = 11
 LSMBLK_DEBUG_EMIT_MODE = 12
 
@@ -228,6 +249,23 @@ def kernel_log(ctx):
     n = U32(0)
     check(lib().lsmblk_ctx_kernel_log(ctx, buf, 256, ctypes.byref(n)), "lsmblk_ctx_kernel_log")
     return {buf[i].name.decode(): (int(buf[i].launches), float(buf[i].ms)) for i in range(n.value)}
+
+
+@contextlib.contextmanager
+def kernel_timing(ctx):
+    """Kernel timing on ctx around the calls made inside: yields a dict that holds kernel_log(ctx) of
+    those calls, {kernel name: (launches, ms)}, once the block has ended."""
+    import torch
+    torch.cuda.synchronize()
+    check(lib().lsmblk_debug_set(ctx, LSMBLK_DEBUG_KERNEL_TIMING, 1))
+    log = {}
+    try:
+        kernel_log(ctx)  # empties the log
+        yield log
+        torch.cuda.synchronize()
+        log.update(kernel_log(ctx))
+    finally:
+        check(lib().lsmblk_debug_set(ctx, LSMBLK_DEBUG_KERNEL_TIMING, 0))
 
 
 def check(status, what=""):

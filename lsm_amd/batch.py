@@ -212,8 +212,13 @@ class KVStream:
                 self.ts[:self.n].cpu().numpy().view(np.uint64))
 
 
+def _stats_words(stats: torch.Tensor) -> list:
+    """The stats words (u64 in an int64 tensor) copied to the host as unsigned ints."""
+    return [int(x) & 0xFFFFFFFFFFFFFFFF for x in stats.cpu().tolist()]
+
+
 def _status(stats: torch.Tensor) -> int:
-    return lib().lsmblk_stats_status(int(stats[3].item()) & 0xFFFFFFFFFFFFFFFF)
+    return lib().lsmblk_stats_status(_stats_words(stats[3:4])[0])
 
 
 def _u32_table(x, dev):

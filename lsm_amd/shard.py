@@ -277,8 +277,8 @@ class RangeShard:
         batch.compact_merge_into(self.kv, self.rs, self.nrun, self.opts, self.range_c, k, self.mstats, self.stream,
                                  ctx=self.ctx, two_end=self.two_end, kept_same=self.ks if self.two else None)
         torch.cuda.synchronize(self.dev)
-        s = self.mstats.cpu().tolist()
-        st = lib().lsmblk_stats_status(s[3] & 0xFFFFFFFFFFFFFFFF)
+        s = batch._stats_words(self.mstats)
+        st = lib().lsmblk_stats_status(s[3])
         if st:
             raise LsmBlkError(st, "compact_merge")
         self.m, self.Kk, self.Vk, self.merged = s[0], s[1], s[2], s[4]
@@ -362,8 +362,8 @@ class RangeShard:
         indices, nseg+1), seg_blk, and whether the first / last segment continue an SST of the
         previous / next range."""
         torch.cuda.synchronize(self.dev)
-        s = self.estats.cpu().tolist()
-        st = lib().lsmblk_stats_status(s[3] & 0xFFFFFFFFFFFFFFFF)
+        s = batch._stats_words(self.estats)
+        st = lib().lsmblk_stats_status(s[3])
         if st:
             raise LsmBlkError(st, "shard_encode")
         nblk, nbytes, nseg = s[0], s[1], s[2]

@@ -24,6 +24,7 @@ Device work goes through liblsmblk.so; the footer / section parsing here is host
 the reference's own (the CRC-32 of those small sections is zlib's, which is crc32fast's).
 """
 import ctypes
+import functools
 import zlib
 
 import numpy as np
@@ -31,9 +32,10 @@ import torch
 
 from . import batch
 from ._lib import (LSMBLK_BOUND_EXCLUDED, LSMBLK_BOUND_INCLUDED, LSMBLK_BOUND_UNBOUNDED, LSMBLK_E_CAPACITY,
-                   LSMBLK_GET_FOUND, LSMBLK_GET_MVCC, LSMBLK_GET_NO_FILTER, LSMBLK_LSM_GET_NEWEST,
-                   LSMBLK_LSM_SCAN_NEWEST, LSMBLK_LSM_SCAN_STATS_WORDS, LSMBLK_SCAN_MVCC, LSMBLK_SCAN_NO_FILTER, GetResultC, LsmBlkError,
-                   LsmGetResultC, LsmScanResultC, LsmViewC, ScanResultC, SstDescC, SstIndexC, check, lib)
+                   LSMBLK_ERR_CAPACITY, LSMBLK_ERR_OVERFLOW, LSMBLK_GET_FOUND, LSMBLK_GET_MVCC, LSMBLK_GET_NO_FILTER,
+                   LSMBLK_LSM_GET_NEWEST, LSMBLK_LSM_SCAN_NEWEST, LSMBLK_LSM_SCAN_STATS_WORDS, LSMBLK_SCAN_MVCC,
+                   LSMBLK_SCAN_NO_FILTER, GetResultC, LsmBlkError, LsmGetResultC, LsmScanResultC, LsmViewC, ScanResultC,
+                   SstDescC, SstIndexC, check, lib)
 
 
 class MemTable:
@@ -226,7 +228,7 @@ class SsTable:
         return batch.decode_blocks(data, rel, tail=4, verify=verify)
 
 
-ERR_CAPACITY = 2  # LSMBLK_ERR_CAPACITY
+ERR_CAPACITY = LSMBLK_ERR_CAPACITY
 GET_FIELDS = ("status", "blk", "ent", "hit_blk", "hit_ent", "vlen", "ts", "val_pos")
 LSM_GET_FIELDS = ("status", "src", "sst", "hit_blk", "hit_ent", "vlen", "ts", "val_pos", "seeks", "bloom_out")
 SCAN_FIELDS = ("status", "blk0", "ent0", "blk1", "ent1", "blocks", "n")
@@ -327,7 +329,7 @@ class SstSet:
         cap = 0
         for _ in range(2):  # the first call sizes the block index
             st = self._open(cap)
-            if not (st[3] & ERR_CAPACITY):
+            if not (st[3] & LSMBLK_ERR_CAPACITY):
                 break
             cap = st[1]
             self.index_t = batch._aligned_empty(cap * ctypes.sizeof(SstIndexC), dev)
@@ -346,7 +348,7 @@ class SstSet:
                       self.file_off.data_ptr(), self.nsst, self.desc_t.data_ptr(), batch._ptr(self.index_t),
                       index_cap, stats.data_ptr(), batch._stream_ptr(self.stream, self.device.index))
         torch.cuda.synchronize(self.device)
-        return [int(x) & 0xFFFFFFFFFFFFFFFF for x in stats.cpu().tolist()]
+        return batch._stats_words(stats)
 
     # ---- what SsTable::open leaves (read back from the descriptors and the index)
     def _file_bytes(self):
@@ -390,23 +392,69 @@ class SstSet:
         return [(int(r["off"]), int(r["end"]), self._slice(fo + int(r["key_pos"]), r["key_len"])) for r in self._records(s)]
 
     # ---- lookups
+    def _set_args(self):
+        """The set's leading arguments of every lookup call."""
+        return (batch._ptr(self.files), self.file_off.data_ptr(), self.nsst, self.desc_t.data_ptr(),
+                batch._ptr(self.index_t))
+
+    def _need_get(self, qkey_off, q_ts, nq, res, res_c, stats, vals, val_cap, val_off):
+        """The checks get_into and lsm_get_into share -> the call's (vals, val_cap, val_off) arguments."""
+        dev = self.device.index
+        batch._need(qkey_off, torch.int32, "qkey_off", dev, nq + 1)
+        batch._need(q_ts, torch.int64, "q_ts", dev, nq)
+        batch._need(res, torch.uint8, "res", dev, nq * ctypes.sizeof(res_c))
+        batch._need(stats, torch.int64, "stats", dev, batch.STATS_WORDS)
+        if vals is None:
+            return None, 0, None
+        batch._need(vals, torch.uint8, "vals", dev, val_cap)
+        batch._need(val_off, torch.int32, "val_off", dev, nq + 1)
+        return vals.data_ptr(), val_cap, val_off.data_ptr()
+
+    def _get_call(self, res_c, into, nq, val_cap, vals):
+        """One point-read call, get_raw's and lsm_get_raw's: `into` is get_into / lsm_get_into bound up
+        to `flags`; allocates the results, calls, synchronizes and reads back."""
+        dev = self.device
+        res = torch.zeros(max(nq, 1) * ctypes.sizeof(res_c), dtype=torch.uint8, device=dev)
+        stats = torch.zeros(batch.STATS_WORDS, dtype=torch.int64, device=dev)
+        vo = None
+        if val_cap is not None:
+            if vals is None:
+                vals = batch._aligned_empty(val_cap, dev)
+            vo = torch.zeros(nq + 1, dtype=torch.int32, device=dev)
+        into(res, stats, vals if val_cap is not None else None, val_cap or 0, vo)
+        torch.cuda.synchronize(dev)
+        r = res.cpu().numpy().view(np.dtype(res_c))[:nq]
+        st = batch._stats_words(stats)
+        return r, vals, (vo.cpu().numpy().view(np.uint32) if vo is not None else None), st
+
+    def _get(self, raw, nq, fields, what, values):
+        """get's and lsm_get's loop: raw(val_cap) is one *_get_raw call; one retry on CAPACITY with the
+        bytes it reported, then the dict of the fields and, with `values`, the value bytes."""
+        cap = 64 * nq + 1024 if values else None
+        for _ in range(2):
+            r, vals, vo, st = raw(cap)
+            if values and st[3] == LSMBLK_ERR_CAPACITY:
+                cap = st[2]
+                continue
+            break
+        if st[3]:
+            raise LsmBlkError(lib().lsmblk_stats_status(st[3]), what)
+        out = {f: r[f].copy() for f in fields}
+        if values:
+            hv = vals[:int(vo[-1])].cpu().numpy() if len(vo) else np.zeros(0, np.uint8)
+            out["val_off"] = vo
+            out["values"] = [hv[vo[i]:vo[i + 1]].tobytes() if r["status"][i] == LSMBLK_GET_FOUND else None
+                             for i in range(nq)]
+        return out
+
     def get_into(self, q_sst, qkeys, qkey_off, q_ts, nq, flags, res, stats, vals=None, val_cap=0, val_off=None):
         """Asynchronous lsmblk_sst_get_batch over device tensors (no host sync): q_sst / qkey_off int32
         (u32), q_ts int64 (u64), res uint8[40 nq], stats int64[4]; vals / val_off None: no gather."""
         dev = self.device.index
         batch._need(q_sst, torch.int32, "q_sst", dev, nq)
-        batch._need(qkey_off, torch.int32, "qkey_off", dev, nq + 1)
-        batch._need(q_ts, torch.int64, "q_ts", dev, nq)
-        batch._need(res, torch.uint8, "res", dev, nq * ctypes.sizeof(GetResultC))
-        batch._need(stats, torch.int64, "stats", dev, batch.STATS_WORDS)
-        if vals is not None:
-            batch._need(vals, torch.uint8, "vals", dev, val_cap)
-            batch._need(val_off, torch.int32, "val_off", dev, nq + 1)
-        batch._native("lsmblk_sst_get_batch", dev, self.stream, batch._ptr(self.files), self.file_off.data_ptr(),
-                      self.nsst, self.desc_t.data_ptr(), batch._ptr(self.index_t), q_sst.data_ptr(), qkeys.data_ptr(),
-                      qkey_off.data_ptr(), q_ts.data_ptr(), nq, flags, res.data_ptr(),
-                      vals.data_ptr() if vals is not None else None, val_cap if vals is not None else 0,
-                      val_off.data_ptr() if vals is not None else None, stats.data_ptr(),
+        tail = self._need_get(qkey_off, q_ts, nq, res, GetResultC, stats, vals, val_cap, val_off)
+        batch._native("lsmblk_sst_get_batch", dev, self.stream, *self._set_args(), q_sst.data_ptr(), qkeys.data_ptr(),
+                      qkey_off.data_ptr(), q_ts.data_ptr(), nq, flags, res.data_ptr(), *tail, stats.data_ptr(),
                       batch._stream_ptr(self.stream, dev))
 
     def upload_queries(self, q_sst, keys, read_ts):
@@ -420,27 +468,20 @@ class SstSet:
         if kb:
             qk[:len(kb)].copy_(torch.frombuffer(bytearray(kb), dtype=torch.uint8))
         qs = batch._u32_table(np.ascontiguousarray(q_sst, np.uint32).reshape(-1) if nq else np.zeros(1, np.uint32), dev)
-        ts = np.broadcast_to(np.asarray(read_ts, np.uint64), (nq,)).copy() if nq else np.zeros(1, np.uint64)
-        qt = torch.from_numpy(ts.view(np.int64)).to(dev)
+        qt = self._read_ts(read_ts, nq)
         return qs, qk, batch._u32_table(ko, dev), qt
+
+    def _read_ts(self, read_ts, nq):
+        """One read_ts for all or one per query -> the int64 (u64) device tensor of nq (never empty)."""
+        ts = np.broadcast_to(np.asarray(read_ts, np.uint64), (nq,)).copy() if nq else np.zeros(1, np.uint64)
+        return torch.from_numpy(ts.view(np.int64)).to(self.device)
 
     def get_raw(self, q_sst, keys, read_ts, flags=0, val_cap=None, vals=None):
         """One lsmblk_sst_get_batch call -> (results as a numpy record array, vals tensor or None,
         val_off numpy or None, stats list); nothing raises on the stats.  val_cap None: no gather."""
-        dev, nq = self.device, len(keys)
+        nq = len(keys)
         qs, qk, qo, qt = self.upload_queries(q_sst, keys, read_ts)
-        res = torch.zeros(max(nq, 1) * ctypes.sizeof(GetResultC), dtype=torch.uint8, device=dev)
-        stats = torch.zeros(batch.STATS_WORDS, dtype=torch.int64, device=dev)
-        vo = None
-        if val_cap is not None:
-            if vals is None:
-                vals = batch._aligned_empty(val_cap, dev)
-            vo = torch.zeros(nq + 1, dtype=torch.int32, device=dev)
-        self.get_into(qs, qk, qo, qt, nq, flags, res, stats, vals if val_cap is not None else None, val_cap or 0, vo)
-        torch.cuda.synchronize(dev)
-        r = res.cpu().numpy().view(np.dtype(GetResultC))[:nq]
-        st = [int(x) & 0xFFFFFFFFFFFFFFFF for x in stats.cpu().tolist()]
-        return r, vals, (vo.cpu().numpy().view(np.uint32) if vo is not None else None), st
+        return self._get_call(GetResultC, functools.partial(self.get_into, qs, qk, qo, qt, nq, flags), nq, val_cap, vals)
 
     def get(self, q_sst, keys, read_ts, *, no_filter=False, mvcc=False, values=True):
         """Batched point lookups: query i = (q_sst[i], keys[i], read_ts[i] or the scalar read_ts) ->
@@ -448,22 +489,8 @@ class SstSet:
         statuses) and, with `values`, "values": a list of the FOUND lookups' value bytes (None for
         the others) and "val_off"."""
         flags = (LSMBLK_GET_NO_FILTER if no_filter else 0) | (LSMBLK_GET_MVCC if mvcc else 0)
-        cap = 64 * len(keys) + 1024 if values else None
-        for _ in range(2):
-            r, vals, vo, st = self.get_raw(q_sst, keys, read_ts, flags, cap)
-            if values and st[3] == ERR_CAPACITY:
-                cap = st[2]
-                continue
-            break
-        if st[3]:
-            raise LsmBlkError(lib().lsmblk_stats_status(st[3]), "sst get")
-        out = {f: r[f].copy() for f in GET_FIELDS}
-        if values:
-            hv = vals[:int(vo[-1])].cpu().numpy() if len(vo) else np.zeros(0, np.uint8)
-            out["val_off"] = vo
-            out["values"] = [hv[vo[i]:vo[i + 1]].tobytes() if r["status"][i] == LSMBLK_GET_FOUND else None
-                             for i in range(len(keys))]
-        return out
+        return self._get(lambda cap: self.get_raw(q_sst, keys, read_ts, flags, cap), len(keys), GET_FIELDS, "sst get",
+                         values)
 
     # ---- point reads over an LSM view
     def view(self, l0, levels, mem=None):
@@ -475,38 +502,19 @@ class SstSet:
         """Asynchronous lsmblk_lsm_get_batch over device tensors (no host sync): qkey_off int32 (u32),
         q_ts int64 (u64), res uint8[48 nq], stats int64[4]; vals / val_off None: no gather."""
         dev = self.device.index
-        batch._need(qkey_off, torch.int32, "qkey_off", dev, nq + 1)
-        batch._need(q_ts, torch.int64, "q_ts", dev, nq)
-        batch._need(res, torch.uint8, "res", dev, nq * ctypes.sizeof(LsmGetResultC))
-        batch._need(stats, torch.int64, "stats", dev, batch.STATS_WORDS)
-        if vals is not None:
-            batch._need(vals, torch.uint8, "vals", dev, val_cap)
-            batch._need(val_off, torch.int32, "val_off", dev, nq + 1)
+        tail = self._need_get(qkey_off, q_ts, nq, res, LsmGetResultC, stats, vals, val_cap, val_off)
         cv = view._c()
-        batch._native("lsmblk_lsm_get_batch", dev, self.stream, batch._ptr(self.files), self.file_off.data_ptr(),
-                      self.nsst, self.desc_t.data_ptr(), batch._ptr(self.index_t), ctypes.byref(cv), qkeys.data_ptr(),
-                      qkey_off.data_ptr(), q_ts.data_ptr(), nq, flags, res.data_ptr(),
-                      vals.data_ptr() if vals is not None else None, val_cap if vals is not None else 0,
-                      val_off.data_ptr() if vals is not None else None, stats.data_ptr(),
+        batch._native("lsmblk_lsm_get_batch", dev, self.stream, *self._set_args(), ctypes.byref(cv), qkeys.data_ptr(),
+                      qkey_off.data_ptr(), q_ts.data_ptr(), nq, flags, res.data_ptr(), *tail, stats.data_ptr(),
                       batch._stream_ptr(self.stream, dev))
 
     def lsm_get_raw(self, view, keys, read_ts, flags=0, val_cap=None, vals=None):
         """One lsmblk_lsm_get_batch call -> (results as a numpy record array, vals tensor or None,
         val_off numpy or None, stats list); nothing raises on the stats.  val_cap None: no gather."""
-        dev, nq = self.device, len(keys)
+        nq = len(keys)
         _, qk, qo, qt = self.upload_queries([0] * nq, keys, read_ts)
-        res = torch.zeros(max(nq, 1) * ctypes.sizeof(LsmGetResultC), dtype=torch.uint8, device=dev)
-        stats = torch.zeros(batch.STATS_WORDS, dtype=torch.int64, device=dev)
-        vo = None
-        if val_cap is not None:
-            if vals is None:
-                vals = batch._aligned_empty(val_cap, dev)
-            vo = torch.zeros(nq + 1, dtype=torch.int32, device=dev)
-        self.lsm_get_into(view, qk, qo, qt, nq, flags, res, stats, vals if val_cap is not None else None, val_cap or 0, vo)
-        torch.cuda.synchronize(dev)
-        r = res.cpu().numpy().view(np.dtype(LsmGetResultC))[:nq]
-        st = [int(x) & 0xFFFFFFFFFFFFFFFF for x in stats.cpu().tolist()]
-        return r, vals, (vo.cpu().numpy().view(np.uint32) if vo is not None else None), st
+        return self._get_call(LsmGetResultC, functools.partial(self.lsm_get_into, view, qk, qo, qt, nq, flags), nq, val_cap,
+                              vals)
 
     def lsm_get(self, view, keys, read_ts, *, mvcc=False, newest=False, values=True):
         """get_with_ts (below the memtables for a view without runs) for a batch of keys: key i at read_ts[i] (or the scalar
@@ -515,24 +523,37 @@ class SstSet:
         the others) and "val_off".  mvcc: the corrected landing per table; newest: the version with
         the largest ts <= read_ts over every source (LSMBLK_LSM_GET_NEWEST)."""
         flags = (LSMBLK_GET_MVCC if mvcc else 0) | (LSMBLK_LSM_GET_NEWEST if newest else 0)
-        cap = 64 * len(keys) + 1024 if values else None
-        for _ in range(2):
-            r, vals, vo, st = self.lsm_get_raw(view, keys, read_ts, flags, cap)
-            if values and st[3] == ERR_CAPACITY:
-                cap = st[2]
-                continue
-            break
-        if st[3]:
-            raise LsmBlkError(lib().lsmblk_stats_status(st[3]), "lsm get")
-        out = {f: r[f].copy() for f in LSM_GET_FIELDS}
-        if values:
-            hv = vals[:int(vo[-1])].cpu().numpy() if len(vo) else np.zeros(0, np.uint8)
-            out["val_off"] = vo
-            out["values"] = [hv[vo[i]:vo[i + 1]].tobytes() if r["status"][i] == LSMBLK_GET_FOUND else None
-                             for i in range(len(keys))]
-        return out
+        return self._get(lambda cap: self.lsm_get_raw(view, keys, read_ts, flags, cap), len(keys), LSM_GET_FIELDS, "lsm get",
+                         values)
 
     # ---- range scans
+    def _need_ranges(self, lkey_off, ukey_off, q_bound, q_ts, nq, res, res_c, seg_start, stats, stats_words):
+        """The checks scan_into and lsm_scan_into share (q_ts None: the call takes none, or none is given)."""
+        dev = self.device.index
+        batch._need(lkey_off, torch.int32, "lkey_off", dev, nq + 1)
+        batch._need(ukey_off, torch.int32, "ukey_off", dev, nq + 1)
+        batch._need(q_bound, torch.int32, "q_bound", dev, nq)
+        if q_ts is not None:
+            batch._need(q_ts, torch.int64, "q_ts", dev, nq)
+        batch._need(res, torch.uint8, "res", dev, nq * ctypes.sizeof(res_c))
+        batch._need(seg_start, torch.int32, "seg_start", dev, nq + 1)
+        batch._need(stats, torch.int64, "stats", dev, stats_words)
+
+    def _stream_arg(self, s, caps, name):
+        """An output stream or None -> the call's argument: its C struct with `caps` (default s.caps())."""
+        if s is None:
+            return None
+        s.check(self.device.index, name, 0)
+        return ctypes.byref(s._c(*(caps if caps is not None else s.caps())))
+
+    @staticmethod
+    def _rows(kv, seg, nq):
+        """Per range q its entries [seg[q], seg[q + 1]) of kv as (key, ts, value)."""
+        keys, ko, vals, vo, ts = kv.to_numpy()
+        kb, vb = keys.tobytes(), vals.tobytes()
+        return [[(kb[ko[i]:ko[i + 1]], int(ts[i]), vb[vo[i]:vo[i + 1]]) for i in range(int(seg[q]), int(seg[q + 1]))]
+                for q in range(nq)]
+
     def scan_into(self, q_sst, lkeys, lkey_off, ukeys, ukey_off, q_bound, nq, flags, res, seg_start, stats,
                   out: batch.KVStream = None, caps=None):
         """Asynchronous lsmblk_sst_scan_batch over device tensors (no host sync): q_sst / lkey_off /
@@ -540,21 +561,11 @@ class SstSet:
         seg_start and the sizes in stats only; caps = (entry_cap, key_cap, val_cap), default out.caps()."""
         dev = self.device.index
         batch._need(q_sst, torch.int32, "q_sst", dev, nq)
-        batch._need(lkey_off, torch.int32, "lkey_off", dev, nq + 1)
-        batch._need(ukey_off, torch.int32, "ukey_off", dev, nq + 1)
-        batch._need(q_bound, torch.int32, "q_bound", dev, nq)
-        batch._need(res, torch.uint8, "res", dev, nq * ctypes.sizeof(ScanResultC))
-        batch._need(seg_start, torch.int32, "seg_start", dev, nq + 1)
-        batch._need(stats, torch.int64, "stats", dev, batch.STATS_WORDS)
-        co = None
-        if out is not None:
-            out.check(dev, "out", 0)
-            co = out._c(*(caps if caps is not None else out.caps()))
-        batch._native("lsmblk_sst_scan_batch", dev, self.stream, batch._ptr(self.files), self.file_off.data_ptr(),
-                      self.nsst, self.desc_t.data_ptr(), batch._ptr(self.index_t), q_sst.data_ptr(), lkeys.data_ptr(),
+        self._need_ranges(lkey_off, ukey_off, q_bound, None, nq, res, ScanResultC, seg_start, stats, batch.STATS_WORDS)
+        batch._native("lsmblk_sst_scan_batch", dev, self.stream, *self._set_args(), q_sst.data_ptr(), lkeys.data_ptr(),
                       lkey_off.data_ptr(), ukeys.data_ptr(), ukey_off.data_ptr(), q_bound.data_ptr(), nq, flags,
-                      res.data_ptr(), ctypes.byref(co) if co is not None else None, seg_start.data_ptr(),
-                      stats.data_ptr(), batch._stream_ptr(self.stream, dev))
+                      res.data_ptr(), self._stream_arg(out, caps, "out"), seg_start.data_ptr(), stats.data_ptr(),
+                      batch._stream_ptr(self.stream, dev))
 
     def upload_ranges(self, q_sst, lower, upper, lower_kind, upper_kind):
         """Host ranges -> the device tensors of scan_into: (q_sst, lkeys, lkey_off, ukeys, ukey_off,
@@ -581,8 +592,8 @@ class SstSet:
         self.scan_into(*t, nq, flags, res, seg, stats, out if caps is not None else None, caps)
         torch.cuda.synchronize(dev)
         r = res.cpu().numpy().view(np.dtype(ScanResultC))[:nq]
-        st = [int(x) & 0xFFFFFFFFFFFFFFFF for x in stats.cpu().tolist()]
-        if caps is not None and not st[3] & (ERR_CAPACITY | 4):
+        st = batch._stats_words(stats)
+        if caps is not None and not st[3] & (LSMBLK_ERR_CAPACITY | LSMBLK_ERR_OVERFLOW):
             out.n = st[0]
         return r, seg.cpu().numpy().view(np.uint32), (out if caps is not None else None), st
 
@@ -597,7 +608,7 @@ class SstSet:
         caps = (64 * nq + 1024, 1024 * nq + 4096, 4096 * nq + 4096)
         for _ in range(2):
             r, seg, kv, st = self.scan_raw(q_sst, lower, upper, lower_kind, upper_kind, flags, caps)
-            if st[3] == ERR_CAPACITY:
+            if st[3] == LSMBLK_ERR_CAPACITY:
                 caps = (st[0], st[1], st[2])
                 continue
             break
@@ -605,11 +616,7 @@ class SstSet:
             raise LsmBlkError(lib().lsmblk_stats_status(st[3]), "sst scan")
         if read_ts is not None and nq:
             kv, seg = batch.read_filter(kv, seg, read_ts, self.stream)
-        keys, ko, vals, vo, ts = kv.to_numpy()
-        kb, vb = keys.tobytes(), vals.tobytes()
-        rows = [[(kb[ko[i]:ko[i + 1]], int(ts[i]), vb[vo[i]:vo[i + 1]]) for i in range(int(seg[q]), int(seg[q + 1]))]
-                for q in range(nq)]
-        return {f: r[f].copy() for f in SCAN_FIELDS}, rows
+        return {f: r[f].copy() for f in SCAN_FIELDS}, self._rows(kv, seg, nq)
 
     # ---- range scans over an LSM view
     def lsm_scan_into(self, view, lkeys, lkey_off, ukeys, ukey_off, q_bound, q_ts, nq, flags, sub_cap, res, seg_start,
@@ -619,27 +626,14 @@ class SstSet:
         stats int64[8]; raw None: the table scans are sized only; out None: sizes only; *_caps =
         (entry_cap, key_cap, val_cap), default the stream's caps()."""
         dev = self.device.index
-        batch._need(lkey_off, torch.int32, "lkey_off", dev, nq + 1)
-        batch._need(ukey_off, torch.int32, "ukey_off", dev, nq + 1)
-        batch._need(q_bound, torch.int32, "q_bound", dev, nq)
-        if q_ts is not None:
-            batch._need(q_ts, torch.int64, "q_ts", dev, nq)
-        batch._need(res, torch.uint8, "res", dev, nq * ctypes.sizeof(LsmScanResultC))
-        batch._need(seg_start, torch.int32, "seg_start", dev, nq + 1)
-        batch._need(stats, torch.int64, "stats", dev, LSMBLK_LSM_SCAN_STATS_WORDS)
-        cs = []
-        for s, caps, name in ((raw, raw_caps, "raw"), (out, out_caps, "out")):
-            if s is not None:
-                s.check(dev, name, 0)
-            cs.append(s._c(*(caps if caps is not None else s.caps())) if s is not None else None)
+        self._need_ranges(lkey_off, ukey_off, q_bound, q_ts, nq, res, LsmScanResultC, seg_start, stats,
+                          LSMBLK_LSM_SCAN_STATS_WORDS)
+        craw, cout = self._stream_arg(raw, raw_caps, "raw"), self._stream_arg(out, out_caps, "out")
         cv = view._c()
-        batch._native("lsmblk_lsm_scan_batch", dev, self.stream, batch._ptr(self.files), self.file_off.data_ptr(),
-                      self.nsst, self.desc_t.data_ptr(), batch._ptr(self.index_t), ctypes.byref(cv), lkeys.data_ptr(),
+        batch._native("lsmblk_lsm_scan_batch", dev, self.stream, *self._set_args(), ctypes.byref(cv), lkeys.data_ptr(),
                       lkey_off.data_ptr(), ukeys.data_ptr(), ukey_off.data_ptr(), q_bound.data_ptr(),
-                      q_ts.data_ptr() if q_ts is not None else None, nq, flags, sub_cap, res.data_ptr(),
-                      ctypes.byref(cs[0]) if cs[0] is not None else None,
-                      ctypes.byref(cs[1]) if cs[1] is not None else None, seg_start.data_ptr(), stats.data_ptr(),
-                      batch._stream_ptr(self.stream, dev))
+                      q_ts.data_ptr() if q_ts is not None else None, nq, flags, sub_cap, res.data_ptr(), craw, cout,
+                      seg_start.data_ptr(), stats.data_ptr(), batch._stream_ptr(self.stream, dev))
 
     def lsm_scan_raw(self, view, lower, upper, lower_kind, upper_kind, read_ts=None, flags=0, sub_cap=None,
                      raw_caps=None, out_caps=None, raw=None, out=None):
@@ -649,10 +643,7 @@ class SstSet:
         stream); None: that stream is not passed.  sub_cap None: view_sub_cap(view, nq)."""
         dev, nq = self.device, len(lower)
         _, lk, lo, uk, uo, bnd = self.upload_ranges([0] * nq, lower, upper, lower_kind, upper_kind)
-        qt = None
-        if read_ts is not None:
-            ts = np.broadcast_to(np.asarray(read_ts, np.uint64), (nq,)).copy() if nq else np.zeros(1, np.uint64)
-            qt = torch.from_numpy(ts.view(np.int64)).to(dev)
+        qt = self._read_ts(read_ts, nq) if read_ts is not None else None
         res = torch.zeros(max(nq, 1) * ctypes.sizeof(LsmScanResultC), dtype=torch.uint8, device=dev)
         seg = torch.zeros(nq + 1, dtype=torch.int32, device=dev)
         stats = torch.zeros(LSMBLK_LSM_SCAN_STATS_WORDS, dtype=torch.int64, device=dev)
@@ -666,8 +657,8 @@ class SstSet:
                            res, seg, stats, raw, out, raw_caps, out_caps)
         torch.cuda.synchronize(dev)
         r = res.cpu().numpy().view(np.dtype(LsmScanResultC))[:nq]
-        st = [int(x) & 0xFFFFFFFFFFFFFFFF for x in stats.cpu().tolist()]
-        if not st[3] & (ERR_CAPACITY | 4):
+        st = batch._stats_words(stats)
+        if not st[3] & (LSMBLK_ERR_CAPACITY | LSMBLK_ERR_OVERFLOW):
             if raw is not None:
                 raw.n = st[4]
             if out is not None:
@@ -693,7 +684,7 @@ class SstSet:
         flags = (LSMBLK_SCAN_MVCC if mvcc else 0) | (LSMBLK_LSM_SCAN_NEWEST if newest else 0)
         for _ in range(2):
             r, seg, _, kv, st = self.lsm_scan_raw(view, lower, upper, lower_kind, upper_kind, read_ts, flags, cap, rc, oc)
-            if st[3] != ERR_CAPACITY:
+            if st[3] != LSMBLK_ERR_CAPACITY:
                 break
             if st[7] > cap:  # no scan ran: the streams' sizes are still unknown
                 cap = st[7]
@@ -704,11 +695,7 @@ class SstSet:
                 oc = (st[0], st[1], st[2])
         if st[3]:
             raise LsmBlkError(lib().lsmblk_stats_status(st[3]), "lsm scan")
-        keys, ko, vals, vo, ts = kv.to_numpy()
-        kb, vb = keys.tobytes(), vals.tobytes()
-        rows = [[(kb[ko[i]:ko[i + 1]], int(ts[i]), vb[vo[i]:vo[i + 1]]) for i in range(int(seg[q]), int(seg[q + 1]))]
-                for q in range(nq)]
-        return {f: r[f].copy() for f in LSM_SCAN_FIELDS}, rows
+        return {f: r[f].copy() for f in LSM_SCAN_FIELDS}, self._rows(kv, seg, nq)
 
 
 def open_compacted(r, device="cuda", stream=None):

@@ -9,21 +9,15 @@ import os
 
 import numpy as np
 import pytest
-import torch
 
 import bench
+from gpu_kit import _need_gpu  # noqa: F401 (autouse)
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
 
 SMALL = ["--gpus", "1", "--blocks", "192", "--segment-bytes", "131072"]
 HEADLINE = ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step")
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a ROCm device")
 
 
 def run(capsys, *argv):

@@ -10,24 +10,18 @@ import pytest
 import torch
 
 import block_rule_cases as brc
+from gpu_kit import _need_gpu  # noqa: F401 (autouse)
 from lsm_amd import batch, sst
-from lsm_amd._lib import LSMBLK_E_MALFORMED, LsmBlkError, lib
+from lsm_amd._lib import LSMBLK_DEBUG_TWO_PASS_DECODE, LSMBLK_ERR_MALFORMED, LSMBLK_E_MALFORMED, LsmBlkError, lib
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
 
-ERR_MALFORMED = 1
 GET_ABSENT, GET_FOUND, GET_TOMBSTONE = 0, 1, 2
 SCAN_OK, SCAN_EMPTY = 0, 1
 NO_FILTER, MVCC = 1, 2
 CAPS = (256, 4096, 16384)
 SST_NAMES = [c.name for c in brc.cases() if c.size != "raw"]
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a ROCm device")
 
 
 def dev_block(block, tail=b""):
@@ -63,11 +57,11 @@ def test_decode(name):
 @pytest.mark.parametrize("name", brc.NAMES)
 def test_two_pass_decode(name):
     ctx = batch._ctx(0)
-    assert lib().lsmblk_debug_set(ctx, 3, 1) == 0  # LSMBLK_DEBUG_TWO_PASS_DECODE
+    assert lib().lsmblk_debug_set(ctx, LSMBLK_DEBUG_TWO_PASS_DECODE, 1) == 0
     try:
         check_decode(name)
     finally:
-        lib().lsmblk_debug_set(ctx, 3, 0)
+        lib().lsmblk_debug_set(ctx, LSMBLK_DEBUG_TWO_PASS_DECODE, 0)
 
 
 @pytest.mark.parametrize("name", brc.NAMES)
@@ -79,11 +73,11 @@ def test_verifying_decode(name):
 def test_two_pass_verifying_decode(name):
     """crc_kernel<true>'s count_block, the fused count of the two-pass verifying decode."""
     ctx = batch._ctx(0)
-    assert lib().lsmblk_debug_set(ctx, 3, 1) == 0  # LSMBLK_DEBUG_TWO_PASS_DECODE
+    assert lib().lsmblk_debug_set(ctx, LSMBLK_DEBUG_TWO_PASS_DECODE, 1) == 0
     try:
         check_decode(name, tail=4, verify=True)
     finally:
-        lib().lsmblk_debug_set(ctx, 3, 0)
+        lib().lsmblk_debug_set(ctx, LSMBLK_DEBUG_TWO_PASS_DECODE, 0)
 
 
 @pytest.mark.parametrize("name", SST_NAMES)
@@ -152,7 +146,7 @@ def test_sst_get(name):
             assert g["values"] == [v or None for _, _, v in ents]
         else:
             r, _, _, st = ss.get_raw([0] + [1] * len(OTHER_KEYS), [c.seek_key] + OTHER_KEYS, 1 << 40, NO_FILTER)
-            assert st[3] == ERR_MALFORMED
+            assert st[3] == LSMBLK_ERR_MALFORMED
             assert r["status"][0] == GET_ABSENT and r["vlen"][0] == 0
             assert r[1:].tobytes() == others.tobytes()  # the other table's keys: answered as before
 
@@ -172,7 +166,7 @@ def test_sst_scan(name):
         assert r["n"].tolist() == [len(ents), len(brc.OTHER_ENTRIES)] and seg.tolist() == [0, len(ents), len(got)]
         assert got == ents + brc.OTHER_ENTRIES
     else:
-        assert st[3] == ERR_MALFORMED
+        assert st[3] == LSMBLK_ERR_MALFORMED
         assert r["status"].tolist() == [SCAN_EMPTY, SCAN_OK] and r["n"].tolist() == [0, len(brc.OTHER_ENTRIES)]
         assert seg.tolist() == [0, 0, len(brc.OTHER_ENTRIES)]
         assert got == brc.OTHER_ENTRIES  # the other table's range: answered as before

@@ -5,18 +5,14 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_kit import _need_gpu  # noqa: F401 (autouse)
 from lsm_amd import batch, synth
-from lsm_amd._lib import LSMBLK_E_INVAL, LSMBLK_E_MALFORMED, LSMBLK_MERGE_RUNS, LSMBLK_MERGE_TWO_LEVEL, LsmBlkError
+from lsm_amd._lib import (LSMBLK_E_INVAL, LSMBLK_E_MALFORMED, LSMBLK_MERGE_RUNS, LSMBLK_MERGE_TWO_LEVEL, LsmBlkError,
+                          kernel_timing)
 from oracle import oracle as O
 from oracle import pyref
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a ROCm device")
 
 
 def kv_runs(runs):
@@ -301,21 +297,14 @@ def test_sst_rotation_large_capacity_long_chain(versions):
     change, 10^4 - 10^5 of them): bit-exact, and no serial chain walk that grows with the capacity
     (K = lc - 9 made each fill thread follow ~sst_cap / 512 elements) -- checked on
     the launches themselves (the context's kernel log), not on wall-clock time."""
-    from lsm_amd._lib import check, kernel_log, lib
     keys, ko, vals, vo, ts, rs = synth.gen_runs(200000 // versions, nrun=2, seed=17, versions=versions)
     kv = O.KV(keys, ko, vals, vo, ts)
     kept = O.gather(kv, O.merge_runs(kv, rs))
     want = O.segment_like_compaction(kept, 64, 1)
     d = to_dev(kept)
     ctx = batch._ctx(torch.cuda.current_device())
-    torch.cuda.synchronize()
-    check(lib().lsmblk_debug_set(ctx, 2, 1))
-    try:
-        kernel_log(ctx)  # empties the log
+    with kernel_timing(ctx) as log:
         got = batch.sst_rotation(d, 64, 1)
-        log = kernel_log(ctx)
-    finally:
-        check(lib().lsmblk_debug_set(ctx, 2, 0))
     np.testing.assert_array_equal(got, want)
     cap = kept.n + 2
     levels = int(np.ceil(np.log2(cap)))

@@ -11,8 +11,9 @@ import pytest
 import torch
 
 import compact_cases as cc
+from gpu_kit import _need_gpu  # noqa: F401 (autouse)
 from lsm_amd import batch
-from lsm_amd._lib import LSMBLK_E_CAPACITY, LSMBLK_MERGE_RUNS, LSMBLK_MERGE_TWO_LEVEL, check, kernel_log, lib
+from lsm_amd._lib import LSMBLK_E_CAPACITY, LSMBLK_MERGE_RUNS, LSMBLK_MERGE_TWO_LEVEL, kernel_timing
 from oracle import oracle as O
 from oracle import pyref
 from test_gpu_compact import assert_kv_equal, check_compact, check_compact_mode, dev_entries, to_dev
@@ -22,25 +23,12 @@ RUNS, TWO = LSMBLK_MERGE_RUNS, LSMBLK_MERGE_TWO_LEVEL
 C = cc.C
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a ROCm device")
-
-
 @contextlib.contextmanager
 def launches():
     """{kernel: launches} of the calls made inside, from the context's kernel log."""
-    ctx = batch._ctx(torch.cuda.current_device())
-    torch.cuda.synchronize()
-    check(lib().lsmblk_debug_set(ctx, 2, 1))
-    log = {}
-    try:
-        kernel_log(ctx)  # empties the log
+    with kernel_timing(batch._ctx(torch.cuda.current_device())) as log:
         yield log
-        log.update({k: v[0] for k, v in kernel_log(ctx).items()})
-    finally:
-        check(lib().lsmblk_debug_set(ctx, 2, 0))
+    log.update({k: v[0] for k, v in log.items()})
 
 
 def gpu_merge(d, rs, mode):

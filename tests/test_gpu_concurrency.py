@@ -14,18 +14,13 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_kit import _need_gpu  # noqa: F401 (autouse)
 from lsm_amd import batch, synth
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
 
 ROUNDS = 3
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a ROCm device")
 
 
 def _case(name):

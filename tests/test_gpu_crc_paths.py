@@ -11,22 +11,17 @@ import pytest
 import torch
 
 import crc_cases as cc
+from gpu_kit import _need_gpu  # noqa: F401 (autouse)
 from lsm_amd import batch
-from lsm_amd._lib import LSMBLK_E_CHECKSUM, LSMBLK_E_MALFORMED, LsmBlkError, lib
+from lsm_amd._lib import LSMBLK_DEBUG_TWO_PASS_DECODE, LSMBLK_E_CHECKSUM, LSMBLK_E_MALFORMED, LsmBlkError, lib
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
 
 FILL = 0x5A5A5A5A     # the crc tensor's guard words
 CRC_GUARD = 4
-TWO_PASS = 3          # LSMBLK_DEBUG_TWO_PASS_DECODE
+TWO_PASS = LSMBLK_DEBUG_TWO_PASS_DECODE
 MODES = ("lagged", "two_pass")   # crc_stream_kernel + the count pass; crc_kernel<true>'s fused count
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a ROCm device")
 
 
 def cu_count():

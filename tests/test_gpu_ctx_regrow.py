@@ -31,6 +31,7 @@ import lsm_get_cases as lc
 import lsm_scan_cases as ls
 import merge_newest_cases as mn
 import scan_cases as sc
+from gpu_kit import _need_gpu, check_stream  # noqa: F401 (_need_gpu: autouse)
 from lsm_amd import batch, shard, sst
 from lsm_amd._lib import (LSMBLK_DEBUG_SCAN_UNITS, LSMBLK_MERGE_NEWEST, LSMBLK_MERGE_RUNS, LSMBLK_MERGE_TWO_LEVEL, lib)
 from oracle import oracle as O
@@ -39,7 +40,6 @@ from test_gpu_compact import assert_kv_equal, check_compact, dev_entries, to_dev
 from test_gpu_crc_paths import decode_mode
 from test_gpu_get import check_open
 from test_gpu_parity import _meta_check, dev_blocks, framed_check, framed_want, slot_check
-from test_gpu_scan import check_stream
 from test_gpu_shard import check_against_single_stream
 
 pytestmark = pytest.mark.gpu
@@ -49,12 +49,6 @@ BS = {"small": 128, "large": 64}
 SML = ("small", "large", "small")
 SCAN_UNITS = 64  # the scans' unit budget here (default 2^17 units = 3 MiB, which no small batch outgrows)
 TS_MAX = (1 << 64) - 1
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a ROCm device")
 
 
 @contextlib.contextmanager
@@ -405,7 +399,7 @@ def scan_step(size):
     assert st == [*caps, 0]
     for f in sc.FIELDS:
         assert r[f].astype(np.uint64).tolist() == [row[f] for row in rows], f
-    check_stream(kv, seg, ents)
+    check_stream(kv, ents, seg)
 
 
 def test_sst_scan():
@@ -429,7 +423,7 @@ def lsm_scan_step(size):
     assert st == [*sizes(out_rows), 0, *sizes(raw_runs), len(raw_runs)]
     for f in ls.FIELDS:
         assert r[f].astype(np.uint64).tolist() == exp[f].tolist(), f
-    check_stream(out, seg, out_rows)
+    check_stream(out, out_rows, seg)
     assert dev_entries(raw) == [e for run in raw_runs for e in run]
 
 

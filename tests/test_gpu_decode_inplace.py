@@ -14,6 +14,7 @@ import torch
 
 import decode_cases as dc
 import decode_inplace_cases as ic
+from gpu_kit import _need_gpu  # noqa: F401 (autouse)
 from lsm_amd import batch
 from lsm_amd._lib import lib
 from oracle import oracle as O
@@ -22,12 +23,6 @@ from test_gpu_decode_routes import TWO_PASS, decode_exact, place
 pytestmark = pytest.mark.gpu
 
 MODES = ("default", "two_pass")
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a ROCm device")
 
 
 @pytest.fixture(scope="module")

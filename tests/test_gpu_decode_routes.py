@@ -15,8 +15,9 @@ import pytest
 import torch
 
 import decode_cases as dc
+from gpu_kit import _need_gpu  # noqa: F401 (autouse)
 from lsm_amd import batch
-from lsm_amd._lib import lib
+from lsm_amd._lib import LSMBLK_DEBUG_DECODE_LAG, LSMBLK_DEBUG_TWO_PASS_DECODE, lib
 from oracle import oracle as O
 from test_gpu_parity import assert_kv_equal, framed_want
 
@@ -24,13 +25,7 @@ pytestmark = pytest.mark.gpu
 
 MODES = ("default", "lag128", "two_pass", "framed_lagged", "framed_two_pass")
 GUARD = 64  # prefilled bytes before and after every output array
-TWO_PASS, LAG = 3, 4  # lsmblk_debug_set keys
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a ROCm device")
+TWO_PASS, LAG = LSMBLK_DEBUG_TWO_PASS_DECODE, LSMBLK_DEBUG_DECODE_LAG
 
 
 @pytest.fixture(scope="module")

@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import path_cases as pc
+from gpu_kit import _need_gpu  # noqa: F401 (autouse)
 from lsm_amd import batch, synth
 from lsm_amd._lib import LSMBLK_DEBUG_EMIT_MODE, LSMBLK_E_CAPACITY, lib
 from oracle import oracle as O
@@ -23,12 +24,6 @@ pytestmark = pytest.mark.gpu
 MODES = [1, 2]
 FILL = 0xA5
 STREAM_CUS = 16  # streams A and B sized as for a 16-CU device: 36352 / >= 1536 blocks
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a ROCm device")
 
 
 @pytest.fixture

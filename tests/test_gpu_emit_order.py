@@ -16,6 +16,7 @@ import pytest
 import torch
 
 import path_cases as pc
+from gpu_kit import _need_gpu  # noqa: F401 (autouse)
 from lsm_amd import batch, synth
 from lsm_amd._lib import LSMBLK_DEBUG_EMIT_MODE, LSMBLK_E_CAPACITY, lib
 from oracle import oracle as O
@@ -26,12 +27,6 @@ pytestmark = pytest.mark.gpu
 MODES = [1, 2]
 NBLK = [1, 7, 8, 9, 63, 64, 65, 127, 128, 129, 200]
 FILL = 0xA5
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a ROCm device")
 
 
 @pytest.fixture

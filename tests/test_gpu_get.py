@@ -10,29 +10,18 @@ import pytest
 import torch
 
 import get_cases as gc
+import gpu_kit as kit
+from gpu_kit import _need_gpu  # noqa: F401 (autouse)
 from lsm_amd import batch, sst
-from lsm_amd._lib import LsmBlkError, SstIndexC
+from lsm_amd._lib import (LSMBLK_ERR_CAPACITY, LSMBLK_ERR_CHECKSUM, LSMBLK_ERR_EMPTY_KEY, LSMBLK_ERR_MALFORMED,
+                          LSMBLK_ERR_SEGMENTS, LsmBlkError, SstIndexC)
 from oracle import pyref
 
 pytestmark = pytest.mark.gpu
 
-ERR_MALFORMED, ERR_CAPACITY, ERR_SEGMENTS, ERR_EMPTY_KEY, ERR_CHECKSUM = 1, 2, 16, 64, 128
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a ROCm device")
-
-
-_sets = {}
-
 
 def opened(name):
-    if name not in _sets:
-        c = gc.case(name)
-        _sets[name] = sst.SstSet(c.files, c.file_off)
-    return _sets[name]
+    return kit.opened_set(gc.case(name), ("get", name))
 
 
 def img_ints(key):
@@ -102,9 +91,9 @@ def corrupt(kind, buf):
     return bytes(b)
 
 
-@pytest.mark.parametrize("kind,flag", [("bloom-body", ERR_CHECKSUM), ("meta-body", ERR_CHECKSUM),
-                                       ("bloom-offset-past-file", ERR_MALFORMED),
-                                       ("meta-offset-past-bloom", ERR_MALFORMED), ("no-blocks", ERR_MALFORMED)])
+@pytest.mark.parametrize("kind,flag", [("bloom-body", LSMBLK_ERR_CHECKSUM), ("meta-body", LSMBLK_ERR_CHECKSUM),
+                                       ("bloom-offset-past-file", LSMBLK_ERR_MALFORMED),
+                                       ("meta-offset-past-bloom", LSMBLK_ERR_MALFORMED), ("no-blocks", LSMBLK_ERR_MALFORMED)])
 def test_a_broken_sst_fails_alone(kind, flag):
     c = gc.case("bs256")
     bad = 1
@@ -163,18 +152,18 @@ def test_error_reports():
     c, ss = gc.case("threshold"), opened("threshold")
     keys, qs, ts = [b"a001", b"a002", b"b-at", b"a003"], [0, 7, 0, 0], [100, 100, 100, 100]
     r, _, _, st = ss.get_raw(qs, keys, ts)
-    assert st[3] == ERR_SEGMENTS and st[0] == 4
+    assert st[3] == LSMBLK_ERR_SEGMENTS and st[0] == 4
     assert r["status"].tolist() == [gc.FOUND, gc.ABSENT, gc.FOUND, gc.FOUND] and r["blk"][1] == gc.NONE
     with pytest.raises(LsmBlkError):
         ss.get(qs, keys, ts)
     r, _, _, st = ss.get_raw([0, 0, 0], [b"a001", b"", b"a003"], 100)
-    assert st[3] == ERR_EMPTY_KEY and r["status"].tolist() == [gc.FOUND, gc.ABSENT, gc.FOUND] and st[1] == 2
+    assert st[3] == LSMBLK_ERR_EMPTY_KEY and r["status"].tolist() == [gc.FOUND, gc.ABSENT, gc.FOUND] and st[1] == 2
     # a too-small value buffer: CAPACITY, the required bytes, nothing written
     exp, values, val_off = gc.expected("threshold", False, False)
     need = int(val_off[-1])
     vals = torch.full((need + 64,), 0xAB, dtype=torch.uint8, device="cuda")
     r, _, vo, st = ss.get_raw(c.q_sst, c.keys, c.read_ts, val_cap=need - 1, vals=vals)
-    assert st[3] == ERR_CAPACITY and st[2] == need and (vals == 0xAB).all()
+    assert st[3] == LSMBLK_ERR_CAPACITY and st[2] == need and (vals == 0xAB).all()
     assert (r["status"] == exp["status"]).all()
     r, _, vo, st = ss.get_raw(c.q_sst, c.keys, c.read_ts, val_cap=need, vals=vals)
     assert st[3] == 0 and st[2] == need and vo.tolist() == val_off.tolist() and st[1] == int((exp["status"] == gc.FOUND).sum())
@@ -187,7 +176,7 @@ def test_too_small_index_reports_the_required_count():
     total = sum(len(s.blocks) for s in c.ssts)
     assert len(ss.index) == total and ss.index_t.numel() >= total * ctypes.sizeof(SstIndexC)
     st = ss._open(total - 1)
-    assert st[3] == ERR_CAPACITY and st[1] == total and st[0] == 0
+    assert st[3] == LSMBLK_ERR_CAPACITY and st[1] == total and st[0] == 0
     st = ss._open(total)
     assert st[3] == 0 and st[0] == len(c.ssts)
 
@@ -202,4 +191,47 @@ def test_empty_batches():
     assert none.nsst == 0 and none.open_stats == [0, 0, 0, 0]
     assert none.get([], [], [])["values"] == []
     r, _, _, st = none.get_raw([0], [b"k"], 1)
-    assert st[3] == ERR_SEGMENTS and r["status"][0] == gc.ABSENT
+    assert st[3] == LSMBLK_ERR_SEGMENTS and r["status"][0] == gc.ABSENT
+
+
+# ------------------------------------------------------------------------------ the wrapper's retry
+RETRY_BYTES = 3 * 2048  # the found values' bytes: more than the wrappers' first 64 * 4 + 1024
+
+
+def capacity_retry_case():
+    """(entries of one SST for block size 4096: 8 keys, one version each, 2048-byte values; 4 query
+    keys, the third absent); test_gpu_lsm_get.py reads the same SST through a view."""
+    ents = [(b"key%02d" % i, 5, bytes([65 + i]) * 2048) for i in range(8)]
+    return ents, [ents[1][0], ents[4][0], b"key04x", ents[6][0]]
+
+
+def check_capacity_retry(ss, raw, get, ents, keys, statuses):
+    """get() -- ss.get or ss.lsm_get over the case -- calls ss.<raw> twice: CAPACITY with the bytes
+    required, then every value."""
+    seen, inner = [], getattr(ss, raw)
+
+    def spy(*a, **kw):
+        r = inner(*a, **kw)
+        seen.append(r[3])
+        return r
+
+    setattr(ss, raw, spy)
+    try:
+        out = get()
+    finally:
+        delattr(ss, raw)
+    assert [st[3] for st in seen] == [LSMBLK_ERR_CAPACITY, 0] and [st[2] for st in seen] == [RETRY_BYTES, RETRY_BYTES]
+    by_key = {k: v for k, _, v in ents}
+    assert out["status"].tolist() == statuses
+    assert out["values"] == [by_key.get(k) for k in keys]
+    assert int(out["val_off"][-1]) == RETRY_BYTES == 6144
+
+
+def test_get_retries_once_on_capacity():
+    """Found values of 6144 bytes against the wrapper's first buffer of 64 * 4 + 1024."""
+    ents, keys = capacity_retry_case()
+    s = gc.make_sst(ents, 4096)
+    ss = sst.SstSet(s.buf, [0, len(s.buf)])
+    statuses = [gc.lookup(s, k, 100, False, False)["status"] for k in keys]
+    assert statuses.count(gc.FOUND) == 3
+    check_capacity_retry(ss, "get_raw", lambda: ss.get([0] * 4, keys, 100), ents, keys, statuses)

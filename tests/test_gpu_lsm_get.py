@@ -9,33 +9,23 @@ import numpy as np
 import pytest
 import torch
 
+import gpu_kit as kit
 import lsm_get_cases as lc
 import scan_cases as sc
+from gpu_kit import _need_gpu  # noqa: F401 (autouse)
 from lsm_amd import batch, sst
-from lsm_amd._lib import LSMBLK_E_INVAL, LSMBLK_GET_NO_FILTER, LsmBlkError, LsmGetResultC
+from lsm_amd._lib import (LSMBLK_ERR_CAPACITY, LSMBLK_ERR_EMPTY_KEY, LSMBLK_ERR_MALFORMED, LSMBLK_ERR_SEGMENTS,
+                          LSMBLK_E_INVAL, LSMBLK_GET_NO_FILTER, LsmBlkError, LsmGetResultC)
+from oracle import pyref
+from test_gpu_get import capacity_retry_case, check_capacity_retry
 
 pytestmark = pytest.mark.gpu
-
-ERR_MALFORMED, ERR_CAPACITY, ERR_SEGMENTS, ERR_EMPTY_KEY = 1, 2, 16, 64
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a ROCm device")
-
-
-_sets = {}
 
 
 def opened(name, bs):
     """(the case, its SstSet, its view); one mixed / edges set per block size."""
-    if (name, bs) not in _sets:
-        v = lc.case(name, bs)
-        ss = sst.SstSet(v.files, v.file_off)
-        assert ss.open_stats[0] == len(v.ssts) and ss.open_stats[3] == 0
-        _sets[name, bs] = (v, ss, ss.view(v.l0, v.levels))
-    return _sets[name, bs]
+    v = lc.case(name, bs)
+    return (v, *kit.opened_view(v, ("lsm_get", name, bs)))
 
 
 def check_fields(got, exp, keys, what=""):
@@ -81,7 +71,7 @@ def test_capacity_contract_and_repeatability(mode):
     assert need > 1
     vals = torch.full((need + 64,), 0xAB, dtype=torch.uint8, device="cuda")
     r, _, vo, st = ss.lsm_get_raw(view, v.keys, v.read_ts, lc.FLAGS[mode], val_cap=need - 1, vals=vals)  # one byte short
-    assert st[3] == ERR_CAPACITY and st[2] == need and st[0] == nq and (vals == 0xAB).all()
+    assert st[3] == LSMBLK_ERR_CAPACITY and st[2] == need and st[0] == nq and (vals == 0xAB).all()
     check_fields(r, exp, v.keys, "short")
     r2, none, vo2, st2 = ss.lsm_get_raw(view, v.keys, v.read_ts, lc.FLAGS[mode])  # vals = NULL
     assert none is None and vo2 is None and st2[3] == 0 and st2[0] == nq and st2[1] == int((exp["status"] == lc.FOUND).sum())
@@ -104,7 +94,7 @@ def test_an_empty_key_is_reported_and_the_others_answer():
     keys = list(v.keys[:40])
     keys[7] = b""
     r, _, _, st = ss.lsm_get_raw(view, keys, v.read_ts[:40])
-    assert st[3] == ERR_EMPTY_KEY and st[0] == 40
+    assert st[3] == LSMBLK_ERR_EMPTY_KEY and st[0] == 40
     assert r["status"][7] == lc.ABSENT and r["src"][7] == lc.NONE and r["seeks"][7] == 0
     ok = np.arange(40) != 7
     for f in lc.FIELDS:
@@ -223,30 +213,30 @@ def refused(ss, view, v, flag):
 
 def test_view_with_an_id_past_the_set():
     v, ss, _ = opened("mixed", 128)
-    refused(ss, ss.view(v.l0 + [ss.nsst], v.levels), v, ERR_SEGMENTS)
-    refused(ss, ss.view(v.l0, [v.levels[0], v.levels[1][:-1] + [0xFFFFFFF0]]), v, ERR_SEGMENTS)
+    refused(ss, ss.view(v.l0 + [ss.nsst], v.levels), v, LSMBLK_ERR_SEGMENTS)
+    refused(ss, ss.view(v.l0, [v.levels[0], v.levels[1][:-1] + [0xFFFFFFF0]]), v, LSMBLK_ERR_SEGMENTS)
 
 
 def test_view_with_a_decreasing_level_start():
     v, ss, _ = opened("mixed", 128)
     view = ss.view(v.l0, v.levels)
     view.level_start_t = batch._u32_table(np.array([0, 5, 3], np.uint32), ss.device)
-    refused(ss, view, v, ERR_SEGMENTS)
+    refused(ss, view, v, LSMBLK_ERR_SEGMENTS)
     view.level_start_t = batch._u32_table(np.array([1, 3, 7], np.uint32), ss.device)  # [0] != 0
-    refused(ss, view, v, ERR_SEGMENTS)
+    refused(ss, view, v, LSMBLK_ERR_SEGMENTS)
 
 
 def test_view_with_swapped_neighbours():
     v, ss, _ = opened("mixed", 128)
     a = v.levels[1]
-    refused(ss, ss.view(v.l0, [v.levels[0], [a[0], a[2], a[1], a[3]]]), v, ERR_MALFORMED)
+    refused(ss, ss.view(v.l0, [v.levels[0], [a[0], a[2], a[1], a[3]]]), v, LSMBLK_ERR_MALFORMED)
 
 
 def test_view_with_overlapping_neighbours():
     v, ss, _ = opened("mixed", 128)
     x, y = sorted(v.l0[:2], key=lambda t: lc.first_key(v.ssts[t]))
     assert lc.first_key(v.ssts[x]) < lc.first_key(v.ssts[y]) <= lc.last_key(v.ssts[x])
-    refused(ss, ss.view([v.l0[2]], [v.levels[0], [x, y]]), v, ERR_MALFORMED)
+    refused(ss, ss.view([v.l0[2]], [v.levels[0], [x, y]]), v, LSMBLK_ERR_MALFORMED)
     # the same two tables in different levels are a valid view
     r, _, _, st = ss.lsm_get_raw(ss.view([v.l0[2]], [[x], [y]]), v.keys[:64], v.read_ts[:64])
     assert st[3] == 0 and st[0] == 64
@@ -257,8 +247,8 @@ def test_view_with_a_table_whose_open_failed(where):
     v = lc.case("mixed", 128)
     bad = v.l0[1] if where == "l0" else v.levels[1][2]
     ss = sst.SstSet(b"".join(sc.corrupt_footer(s.buf) if t == bad else s.buf for t, s in enumerate(v.ssts)), v.file_off)
-    assert ss.err[bad] == ERR_MALFORMED and ss.open_stats[0] == len(v.ssts) - 1
-    refused(ss, ss.view(v.l0, v.levels), v, ERR_MALFORMED)
+    assert ss.err[bad] == LSMBLK_ERR_MALFORMED and ss.open_stats[0] == len(v.ssts) - 1
+    refused(ss, ss.view(v.l0, v.levels), v, LSMBLK_ERR_MALFORMED)
     # a view of the same set without that table answers
     l0 = [t for t in v.l0 if t != bad]
     levels = [[t for t in lv if t != bad] for lv in v.levels]
@@ -266,3 +256,13 @@ def test_view_with_a_table_whose_open_failed(where):
     rws = [lc.closed(lc.View("", v.ssts, l0, levels, [], []), k, ts, "default") for k, ts in zip(v.keys, v.read_ts)]
     assert st[3] == 0
     check_fields(r, lc.arrays(v, rws)[0], v.keys)
+
+
+def test_lsm_get_retries_once_on_capacity():
+    """Found values of 6144 bytes against the wrapper's first buffer of 64 * 4 + 1024."""
+    ents, keys = capacity_retry_case()
+    buf = pyref.sst_file(ents, 4096)
+    ss = sst.SstSet(buf, [0, len(buf)])
+    view = ss.view([0], [])
+    statuses = [lc.FOUND, lc.FOUND, lc.ABSENT, lc.FOUND]
+    check_capacity_retry(ss, "lsm_get_raw", lambda: ss.lsm_get(view, keys, 100), ents, keys, statuses)

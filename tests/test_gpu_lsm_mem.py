@@ -12,22 +12,13 @@ import torch
 
 import lsm_mem_cases as mc
 import scan_cases as sc
+from gpu_kit import (GUARD, _need_gpu, all_empty, check_results, check_stream,  # noqa: F401 (_need_gpu: autouse)
+                     guarded, opened_view, sizes_of, untouched)
 from lsm_amd import batch, sst
-from lsm_amd._lib import LSMBLK_E_INVAL, KVStreamC, LsmBlkError, LsmGetResultC, LsmScanResultC, LsmViewC
+from lsm_amd._lib import (LSMBLK_ERR_CAPACITY, LSMBLK_ERR_SEGMENTS, LSMBLK_E_INVAL, KVStreamC, LsmBlkError,
+                          LsmGetResultC, LsmScanResultC, LsmViewC)
 
 pytestmark = pytest.mark.gpu
-
-ERR_CAPACITY, ERR_SEGMENTS = 2, 16
-GUARD = 0xAB
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a ROCm device")
-
-
-_sets = {}
 
 
 def device_runs(c):
@@ -40,14 +31,8 @@ def device_runs(c):
 def opened(name, bs):
     """(the case, the SstSet of its tables, its view with the runs); tables of the same view are opened once."""
     c = mc.case(name, bs)
-    key = (c.view.name, bs)
-    if key not in _sets:
-        ss = sst.SstSet(c.view.files, c.view.file_off)
-        assert ss.open_stats[0] == len(c.view.ssts) and ss.open_stats[3] == 0
-        _sets[key] = ss
-    if (name, bs, "view") not in _sets:
-        _sets[name, bs, "view"] = _sets[key].view(c.view.l0, c.view.levels, mem=device_runs(c))
-    return c, _sets[key], _sets[name, bs, "view"]
+    return (c, *opened_view(c.view, ("lsm_mem", name, bs), mem=lambda: device_runs(c),
+                            set_key=("lsm_mem", c.view.name, bs)))
 
 
 def check_fields(got, exp, keys, what=""):
@@ -89,7 +74,7 @@ def test_get_capacity_carries_the_bytes_and_writes_nothing(mode):
     assert 0 < mem_bytes < need  # values of both arenas
     vals = torch.full((need + 64,), GUARD, dtype=torch.uint8, device="cuda")
     r, _, vo, st = ss.lsm_get_raw(view, c.keys, c.read_ts, mc.GET_FLAGS[mode], val_cap=need - 1, vals=vals)  # one byte short
-    assert st == [nq, int((exp["status"] == mc.FOUND).sum()), need, ERR_CAPACITY] and (vals == GUARD).all()
+    assert st == [nq, int((exp["status"] == mc.FOUND).sum()), need, LSMBLK_ERR_CAPACITY] and (vals == GUARD).all()
     check_fields(r, exp, c.keys, "short")
     r2, none, vo2, st2 = ss.lsm_get_raw(view, c.keys, c.read_ts, mc.GET_FLAGS[mode])  # vals = NULL
     assert none is None and vo2 is None and st2 == [nq, st[1], 0, 0]
@@ -97,53 +82,12 @@ def test_get_capacity_carries_the_bytes_and_writes_nothing(mode):
 
 
 # ------------------------------------------------------------------------------ range scans
-def sizes_of(rows):
-    kb, ko, vb, vo, ts, seg = sc.stream_of(rows)
-    return len(ts), len(kb), len(vb)
-
-
 def scan(ss, view, c, sel, mode, raw_caps, out_caps, **kw):
     s = c.scan
     pick = lambda x: [x[i] for i in sel]
     flags, filt = mc.scan_mode_args(mode)
     return ss.lsm_scan_raw(view, pick(s.lower), pick(s.upper), pick(s.lkind), pick(s.ukind), pick(s.read_ts) if filt else None,
                            flags, raw_caps=raw_caps, out_caps=out_caps, **kw)
-
-
-def check_results(r, exp, fields=mc.SCAN_FIELDS):
-    for f in fields:
-        bad = np.nonzero(r[f].astype(np.uint64) != exp[f])[0]
-        assert not len(bad), (f, bad[:5], r[f][bad[:5]], exp[f][bad[:5]])
-
-
-def check_stream(kv, rows, seg=None):
-    kb, ko, vb, vo, ts, want_seg = sc.stream_of(rows)
-    if seg is not None:
-        assert seg.tolist() == want_seg.tolist()
-    assert kv.n == len(ts)
-    gk, gko, gv, gvo, gts = kv.to_numpy()
-    assert gko.tolist() == ko.tolist() and gvo.tolist() == vo.tolist() and gts.tolist() == ts.tolist()
-    assert gk.tobytes() == kb and gv.tobytes() == vb
-
-
-def guarded(n, kb, vb, dev, lead=0):
-    """A stream whose every word is a sentinel, its arenas `lead` bytes past a 16-byte boundary."""
-    return batch.KVStream(torch.full((kb + 64 + lead,), GUARD, dtype=torch.uint8, device=dev)[lead:],
-                          torch.full((n + 2,), -1, dtype=torch.int32, device=dev),
-                          torch.full((vb + 64 + lead,), GUARD, dtype=torch.uint8, device=dev)[lead:],
-                          torch.full((n + 2,), -1, dtype=torch.int32, device=dev),
-                          torch.full((n + 1,), -1, dtype=torch.int64, device=dev), 0)
-
-
-def untouched(kv, offsets=True):
-    ok = bool((kv.keys == GUARD).all() and (kv.vals == GUARD).all() and (kv.ts == -1).all())
-    return ok and (not offsets or bool((kv.key_off == -1).all() and (kv.val_off == -1).all()))
-
-
-def all_empty(r, seg, nq):
-    assert (r["status"] == mc.EMPTY).all() and seg.tolist() == [0] * (nq + 1)
-    for f in ("sources", "raw", "merged", "n"):
-        assert (r[f] == 0).all(), f
 
 
 @pytest.mark.parametrize("mode", mc.SCAN_MODES)
@@ -155,7 +99,7 @@ def test_scan_every_field_and_byte_equals_the_closed_form(name, bs, mode):
     raw, out = guarded(rn, rkb, rvb, ss.device, 3), guarded(n, kb, vb, ss.device, 5)  # exact capacities, unaligned arenas
     r, seg, raw, out, st = scan(ss, view, c, range(len(c.scan)), mode, (rn, rkb, rvb), (n, kb, vb), raw=raw, out=out)
     assert st == [n, kb, vb, 0, rn, rkb, rvb, len(raw_runs)]
-    check_results(r, exp)
+    check_results(r, exp, mc.SCAN_FIELDS)
     check_stream(out, out_rows, seg)
     check_stream(raw, raw_runs)
     assert (out.keys[kb:] == GUARD).all() and (out.vals[vb:] == GUARD).all()
@@ -181,11 +125,11 @@ def test_scan_three_stage_capacity_contract():
     # no stream at all: the table scans' sizes, the runs' slices among them
     r, seg, _, _, st = scan(ss, view, c, sel, "mvcc", None, None)
     assert st == [0, 0, 0, 0, rn, rkb, rvb, subs] and seg.tolist() == [0] * (nq + 1)
-    check_results(r, exp, fields=("sources", "raw"))
+    check_results(r, exp, ("sources", "raw"))
     # sub_cap one short of stats[7]: no scan runs
     raw, out = guarded(rn, rkb, rvb, dev), guarded(n, kb, vb, dev)
     r, seg, _, _, st = scan(ss, view, c, sel, "mvcc", (rn, rkb, rvb), (n, kb, vb), sub_cap=subs - 1, raw=raw, out=out)
-    assert st[3] == ERR_CAPACITY and st[7] == subs
+    assert st[3] == LSMBLK_ERR_CAPACITY and st[7] == subs
     all_empty(r, seg, nq)
     assert untouched(raw, offsets=False) and untouched(out, offsets=False)
     # a capacity of raw one short
@@ -194,8 +138,8 @@ def test_scan_three_stage_capacity_contract():
         caps[short] -= 1
         raw, out = guarded(rn, rkb, rvb, dev), guarded(n, kb, vb, dev)
         r, seg, _, _, st = scan(ss, view, c, sel, "mvcc", tuple(caps), (n, kb, vb), raw=raw, out=out)
-        assert st == [0, 0, 0, ERR_CAPACITY, rn, rkb, rvb, subs] and seg.tolist() == [0] * (nq + 1), short
-        check_results(r, exp, fields=("sources", "raw"))
+        assert st == [0, 0, 0, LSMBLK_ERR_CAPACITY, rn, rkb, rvb, subs] and seg.tolist() == [0] * (nq + 1), short
+        check_results(r, exp, ("sources", "raw"))
         assert (r["merged"] == 0).all() and (r["n"] == 0).all() and (r["status"] == mc.EMPTY).all()
         assert untouched(raw), short
     # a capacity of out one short
@@ -204,8 +148,8 @@ def test_scan_three_stage_capacity_contract():
         caps[short] -= 1
         raw, out = guarded(rn, rkb, rvb, dev), guarded(n, kb, vb, dev)
         r, seg, raw, _, st = scan(ss, view, c, sel, "mvcc", (rn, rkb, rvb), tuple(caps), raw=raw, out=out)
-        assert st == [n, kb, vb, ERR_CAPACITY, rn, rkb, rvb, subs] and seg.tolist() == want_seg, short
-        check_results(r, exp)
+        assert st == [n, kb, vb, LSMBLK_ERR_CAPACITY, rn, rkb, rvb, subs] and seg.tolist() == want_seg, short
+        check_results(r, exp, mc.SCAN_FIELDS)
         assert untouched(out), short
         raw.n = rn
         check_stream(raw, raw_runs)
@@ -325,14 +269,14 @@ def test_a_bad_mem_start_is_refused_by_the_view_check(start):
     view = ss.view(c.view.l0, c.view.levels, mem=(kv, batch._u32_table(np.array(start, np.uint32), ss.device)))
     nq = 40
     r, _, vo, st = ss.lsm_get_raw(view, c.keys[:nq], c.read_ts[:nq], 2, val_cap=4096)
-    assert st == [nq, 0, 0, ERR_SEGMENTS]
+    assert st == [nq, 0, 0, LSMBLK_ERR_SEGMENTS]
     assert (r["status"] == mc.ABSENT).all() and (r["vlen"] == 0).all() and (r["seeks"] == 0).all() and (r["bloom_out"] == 0).all()
     for f in ("src", "sst", "hit_blk", "hit_ent"):
         assert (r[f] == mc.NONE).all(), f
     assert vo.tolist() == [0] * (nq + 1)
     for mode in mc.SCAN_MODES:
         r, seg, raw, out, st = scan(ss, view, c, range(nq), mode, (4096, 65536, 65536), (4096, 65536, 65536))
-        assert st == [0, 0, 0, ERR_SEGMENTS, 0, 0, 0, 0], mode
+        assert st == [0, 0, 0, LSMBLK_ERR_SEGMENTS, 0, 0, 0, 0], mode
         all_empty(r, seg, nq)
     with pytest.raises(LsmBlkError):
         ss.lsm_get(view, c.keys[:nq], c.read_ts[:nq])

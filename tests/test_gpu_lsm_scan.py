@@ -10,37 +10,19 @@ import torch
 import lsm_get_cases as lc
 import lsm_scan_cases as ls
 import scan_cases as sc
+from gpu_kit import (GUARD, _need_gpu, all_empty, check_results, check_stream,  # noqa: F401 (_need_gpu: autouse)
+                     guarded, opened_view, sizes_of, untouched)
 from lsm_amd import batch, sst
-from lsm_amd._lib import LSMBLK_E_INVAL, LSMBLK_SCAN_NO_FILTER, LsmBlkError
+from lsm_amd._lib import (LSMBLK_ERR_CAPACITY, LSMBLK_ERR_EMPTY_KEY, LSMBLK_ERR_MALFORMED, LSMBLK_ERR_SEGMENTS,
+                          LSMBLK_E_INVAL, LSMBLK_SCAN_NO_FILTER, LsmBlkError)
 
 pytestmark = pytest.mark.gpu
-
-ERR_MALFORMED, ERR_CAPACITY, ERR_SEGMENTS, ERR_EMPTY_KEY = 1, 2, 16, 64
-GUARD = 0xAB
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a ROCm device")
-
-
-_sets = {}
 
 
 def opened(name, bs):
     """(the case, its SstSet, its view)"""
-    if (name, bs) not in _sets:
-        c = ls.case(name, bs)
-        ss = sst.SstSet(c.view.files, c.view.file_off)
-        assert ss.open_stats[0] == len(c.view.ssts) and ss.open_stats[3] == 0
-        _sets[name, bs] = (c, ss, ss.view(c.view.l0, c.view.levels))
-    return _sets[name, bs]
-
-
-def sizes_of(rows):
-    kb, ko, vb, vo, ts, seg = sc.stream_of(rows)
-    return len(ts), len(kb), len(vb)
+    c = ls.case(name, bs)
+    return (c, *opened_view(c.view, ("lsm_scan", name, bs)))
 
 
 def flags_of(mode):
@@ -54,43 +36,6 @@ def run(ss, view, c, sel, mode, raw_caps, out_caps, **kw):
                            raw_caps=raw_caps, out_caps=out_caps, **kw)
 
 
-def check_results(r, exp, sel=None, fields=ls.FIELDS):
-    for f in fields:
-        want = exp[f] if sel is None else exp[f][sel]
-        bad = np.nonzero(r[f].astype(np.uint64) != want)[0]
-        assert not len(bad), (f, bad[:5], r[f][bad[:5]], want[bad[:5]])
-
-
-def check_stream(kv, rows, seg=None):
-    kb, ko, vb, vo, ts, want_seg = sc.stream_of(rows)
-    if seg is not None:
-        assert seg.tolist() == want_seg.tolist()
-    assert kv.n == len(ts)
-    gk, gko, gv, gvo, gts = kv.to_numpy()
-    assert gko.tolist() == ko.tolist() and gvo.tolist() == vo.tolist() and gts.tolist() == ts.tolist()
-    assert gk.tobytes() == kb and gv.tobytes() == vb
-
-
-def guarded(n, kb, vb, dev):
-    """A stream whose every word is a sentinel."""
-    return batch.KVStream(torch.full((kb + 64,), GUARD, dtype=torch.uint8, device=dev),
-                          torch.full((n + 2,), -1, dtype=torch.int32, device=dev),
-                          torch.full((vb + 64,), GUARD, dtype=torch.uint8, device=dev),
-                          torch.full((n + 2,), -1, dtype=torch.int32, device=dev),
-                          torch.full((n + 1,), -1, dtype=torch.int64, device=dev), 0)
-
-
-def untouched(kv, offsets=True):
-    ok = bool((kv.keys == GUARD).all() and (kv.vals == GUARD).all() and (kv.ts == -1).all())
-    return ok and (not offsets or bool((kv.key_off == -1).all() and (kv.val_off == -1).all()))
-
-
-def all_empty(r, seg, nq):
-    assert (r["status"] == ls.EMPTY).all() and seg.tolist() == [0] * (nq + 1)
-    for f in ("sources", "raw", "merged", "n"):
-        assert (r[f] == 0).all(), f
-
-
 @pytest.mark.parametrize("mode", ls.MODES)
 @pytest.mark.parametrize("name,bs", ls.CASES)
 def test_every_field_and_byte_equals_the_expectation(name, bs, mode):
@@ -100,7 +45,7 @@ def test_every_field_and_byte_equals_the_expectation(name, bs, mode):
     rn, rkb, rvb = sizes_of(raw_runs)
     r, seg, raw, out, st = run(ss, view, c, range(len(c)), mode, (rn, rkb, rvb), (n, kb, vb))  # exact capacities
     assert st == [n, kb, vb, 0, rn, rkb, rvb, len(raw_runs)]
-    check_results(r, exp)
+    check_results(r, exp, ls.FIELDS)
     check_stream(out, out_rows, seg)
     check_stream(raw, raw_runs)
     if mode == "merged":
@@ -120,7 +65,7 @@ def test_query_counts(nq):
     exp, out_rows, raw_runs = ls.arrays(rws)
     r, seg, raw, out, st = run(ss, view, c, sel, "mvcc", sizes_of(raw_runs), sizes_of(out_rows))
     assert st == [*sizes_of(out_rows), 0, *sizes_of(raw_runs), len(raw_runs)]
-    check_results(r, exp)
+    check_results(r, exp, ls.FIELDS)
     check_stream(out, out_rows, seg)
     check_stream(raw, raw_runs)
 
@@ -136,17 +81,17 @@ def test_sizing_calls_and_the_capacity_contract():
     # no stream at all: the table scans' sizes
     r, seg, _, _, st = run(ss, view, c, sel, "default", None, None)
     assert st == [0, 0, 0, 0, rn, rkb, rvb, subs] and seg.tolist() == [0] * (nq + 1)
-    check_results(r, exp, fields=("sources", "raw"))
+    check_results(r, exp, ("sources", "raw"))
     assert (r["merged"] == 0).all() and (r["n"] == 0).all()
     # out = NULL: every size, res and seg_start
     r, seg, raw, out, st = run(ss, view, c, sel, "default", (rn, rkb, rvb), None)
     assert out is None and st == full and seg.tolist() == want_seg
-    check_results(r, exp)
+    check_results(r, exp, ls.FIELDS)
     check_stream(raw, raw_runs)
     # sub_cap one short: no scan runs
     raw, out = guarded(rn, rkb, rvb, dev), guarded(n, kb, vb, dev)
     r, seg, _, _, st = run(ss, view, c, sel, "default", (rn, rkb, rvb), (n, kb, vb), sub_cap=subs - 1, raw=raw, out=out)
-    assert st[3] == ERR_CAPACITY and st[7] == subs
+    assert st[3] == LSMBLK_ERR_CAPACITY and st[7] == subs
     all_empty(r, seg, nq)
     assert untouched(raw, offsets=False) and untouched(out, offsets=False)
     # a capacity of raw one short
@@ -155,8 +100,8 @@ def test_sizing_calls_and_the_capacity_contract():
         caps[short] -= 1
         raw, out = guarded(rn, rkb, rvb, dev), guarded(n, kb, vb, dev)
         r, seg, _, _, st = run(ss, view, c, sel, "default", tuple(caps), (n, kb, vb), raw=raw, out=out)
-        assert st == [0, 0, 0, ERR_CAPACITY, rn, rkb, rvb, subs] and seg.tolist() == [0] * (nq + 1), short
-        check_results(r, exp, fields=("sources", "raw"))
+        assert st == [0, 0, 0, LSMBLK_ERR_CAPACITY, rn, rkb, rvb, subs] and seg.tolist() == [0] * (nq + 1), short
+        check_results(r, exp, ("sources", "raw"))
         assert (r["merged"] == 0).all() and (r["n"] == 0).all() and (r["status"] == ls.EMPTY).all()
         assert untouched(raw), short
     # a capacity of out one short
@@ -165,8 +110,8 @@ def test_sizing_calls_and_the_capacity_contract():
         caps[short] -= 1
         raw, out = guarded(rn, rkb, rvb, dev), guarded(n, kb, vb, dev)
         r, seg, raw, _, st = run(ss, view, c, sel, "default", (rn, rkb, rvb), tuple(caps), raw=raw, out=out)
-        assert st == [n, kb, vb, ERR_CAPACITY, rn, rkb, rvb, subs] and seg.tolist() == want_seg, short
-        check_results(r, exp)
+        assert st == [n, kb, vb, LSMBLK_ERR_CAPACITY, rn, rkb, rvb, subs] and seg.tolist() == want_seg, short
+        check_results(r, exp, ls.FIELDS)
         assert untouched(out), short
         raw.n = rn
         check_stream(raw, raw_runs)
@@ -194,14 +139,14 @@ def refused(ss, view, c, flag):
 def test_view_with_an_id_past_the_set():
     c, ss, _ = opened("mixed", 128)
     v = c.view
-    refused(ss, ss.view(v.l0 + [ss.nsst], v.levels), c, ERR_SEGMENTS)
+    refused(ss, ss.view(v.l0 + [ss.nsst], v.levels), c, LSMBLK_ERR_SEGMENTS)
 
 
 def test_view_with_a_decreasing_level_start():
     c, ss, _ = opened("mixed", 128)
     view = ss.view(c.view.l0, c.view.levels)
     view.level_start_t = batch._u32_table(np.array([0, 5, 3], np.uint32), ss.device)
-    refused(ss, view, c, ERR_SEGMENTS)
+    refused(ss, view, c, LSMBLK_ERR_SEGMENTS)
 
 
 def test_view_with_overlapping_neighbours():
@@ -209,7 +154,7 @@ def test_view_with_overlapping_neighbours():
     v = c.view
     x, y = sorted(v.l0[:2], key=lambda t: lc.first_key(v.ssts[t]))
     assert lc.first_key(v.ssts[x]) < lc.first_key(v.ssts[y]) <= lc.last_key(v.ssts[x])
-    refused(ss, ss.view([v.l0[2]], [v.levels[0], [x, y]]), c, ERR_MALFORMED)
+    refused(ss, ss.view([v.l0[2]], [v.levels[0], [x, y]]), c, LSMBLK_ERR_MALFORMED)
 
 
 # ------------------------------------------------------------------------------ bad ranges
@@ -232,13 +177,13 @@ def with_one_bad_range(flag, lk, lo, uk, up):
 
 
 def test_a_bound_kind_of_3():
-    with_one_bad_range(ERR_SEGMENTS, 3, b"a", sc.INCLUDED, b"b")
-    with_one_bad_range(ERR_SEGMENTS, sc.UNBOUNDED, b"", 3, b"b")
+    with_one_bad_range(LSMBLK_ERR_SEGMENTS, 3, b"a", sc.INCLUDED, b"b")
+    with_one_bad_range(LSMBLK_ERR_SEGMENTS, sc.UNBOUNDED, b"", 3, b"b")
 
 
 def test_an_empty_bounded_key():
-    with_one_bad_range(ERR_EMPTY_KEY, sc.INCLUDED, b"", sc.UNBOUNDED, b"")
-    with_one_bad_range(ERR_EMPTY_KEY, sc.INCLUDED, b"a", sc.EXCLUDED, b"")
+    with_one_bad_range(LSMBLK_ERR_EMPTY_KEY, sc.INCLUDED, b"", sc.UNBOUNDED, b"")
+    with_one_bad_range(LSMBLK_ERR_EMPTY_KEY, sc.INCLUDED, b"a", sc.EXCLUDED, b"")
 
 
 def test_a_malformed_block_empties_its_ranges_only():
@@ -270,9 +215,9 @@ def test_a_malformed_block_empties_its_ranges_only():
     ts = pick(c.read_ts) + [ls.TS_MAX] * len(dirty)
     r, seg, _, out, st = ss.lsm_scan_raw(view, lower, upper, lkind, ukind, ts, 2, raw_caps=(20000, 400000, 800000),
                                          out_caps=(20000, 400000, 800000))
-    assert st[3] == ERR_MALFORMED
+    assert st[3] == LSMBLK_ERR_MALFORMED
     exp, out_rows, _ = ls.arrays([rws[i] for i in clean])
-    check_results(r[:len(clean)], exp)
+    check_results(r[:len(clean)], exp, ls.FIELDS)
     check_stream(out, out_rows + [[] for _ in dirty], seg)
     tail = r[len(clean):]
     assert (tail["status"] == ls.EMPTY).all() and all((tail[f] == 0).all() for f in ("sources", "raw", "merged", "n"))
@@ -310,11 +255,11 @@ def test_workspace_regrowth_on_a_non_default_stream():
         e1, o1, r1 = ls.arrays(rws)
         r, seg, raw, out, st = run(ss, view, c, small, "default", sizes_of(r1), sizes_of(o1))
         assert st[3] == 0
-        check_results(r, e1)
+        check_results(r, e1, ls.FIELDS)
         check_stream(out, o1, seg)
         r, seg, raw, out, st = run(ss, view, c, range(len(c)), "default", sizes_of(raw_runs), sizes_of(out_rows))
         assert st == [*sizes_of(out_rows), 0, *sizes_of(raw_runs), len(raw_runs)]
-        check_results(r, exp)
+        check_results(r, exp, ls.FIELDS)
         check_stream(out, out_rows, seg)
         check_stream(raw, raw_runs)
     torch.cuda.synchronize()

@@ -5,44 +5,25 @@ out and raw streams with and without q_ts, the composition with lsmblk_read_filt
 with the NEWEST point read, the capacity contract, the flag bits and a malformed block."""
 import numpy as np
 import pytest
-import torch
 
 import lsm_scan_cases as ls
 import lsm_scan_newest_cases as ln
 import scan_cases as sc
+from gpu_kit import (GUARD, _need_gpu, all_empty, check_results, check_stream,  # noqa: F401 (_need_gpu: autouse)
+                     guarded, opened_view, sizes_of, untouched)
 from lsm_amd import batch, sst
-from lsm_amd._lib import (LSMBLK_E_INVAL, LSMBLK_GET_FOUND, LSMBLK_LSM_SCAN_NEWEST, LSMBLK_SCAN_MVCC, LSMBLK_SCAN_NO_FILTER,
-                          LsmBlkError)
+from lsm_amd._lib import (LSMBLK_ERR_CAPACITY, LSMBLK_ERR_MALFORMED, LSMBLK_E_INVAL, LSMBLK_GET_FOUND,
+                          LSMBLK_LSM_SCAN_NEWEST, LSMBLK_SCAN_MVCC, LSMBLK_SCAN_NO_FILTER, LsmBlkError)
 
 pytestmark = pytest.mark.gpu
 
-ERR_MALFORMED, ERR_CAPACITY = 1, 2
-GUARD = 0xAB
 NEWEST = LSMBLK_LSM_SCAN_NEWEST
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a ROCm device")
-
-
-_sets = {}
 
 
 def opened(name, bs):
     """(the case, its SstSet, its view)"""
-    if (name, bs) not in _sets:
-        c = ln.case(name, bs)
-        ss = sst.SstSet(c.view.files, c.view.file_off)
-        assert ss.open_stats[0] == len(c.view.ssts) and ss.open_stats[3] == 0
-        _sets[name, bs] = (c, ss, ss.view(c.view.l0, c.view.levels))
-    return _sets[name, bs]
-
-
-def sizes_of(rows):
-    kb, ko, vb, vo, ts, seg = sc.stream_of(rows)
-    return len(ts), len(kb), len(vb)
+    c = ln.case(name, bs)
+    return (c, *opened_view(c.view, ("lsm_scan_newest", name, bs)))
 
 
 def run(ss, view, c, sel, mode, raw_caps, out_caps, flags=NEWEST, **kw):
@@ -52,46 +33,10 @@ def run(ss, view, c, sel, mode, raw_caps, out_caps, flags=NEWEST, **kw):
                            out_caps=out_caps, **kw)
 
 
-def check_results(r, exp, fields=ln.FIELDS):
-    for f in fields:
-        bad = np.nonzero(r[f].astype(np.uint64) != exp[f])[0]
-        assert not len(bad), (f, bad[:5], r[f][bad[:5]], exp[f][bad[:5]])
-
-
-def check_stream(kv, rows, seg=None):
-    kb, ko, vb, vo, ts, want_seg = sc.stream_of(rows)
-    if seg is not None:
-        assert seg.tolist() == want_seg.tolist()
-    assert kv.n == len(ts)
-    gk, gko, gv, gvo, gts = kv.to_numpy()
-    assert gko.tolist() == ko.tolist() and gvo.tolist() == vo.tolist() and gts.tolist() == ts.tolist()
-    assert gk.tobytes() == kb and gv.tobytes() == vb
-
-
 def same_stream(a, b):
     assert a.n == b.n
     for x, y in zip(a.to_numpy(), b.to_numpy()):
         assert x.tobytes() == y.tobytes()
-
-
-def guarded(n, kb, vb, dev):
-    """A stream whose every word is a sentinel."""
-    return batch.KVStream(torch.full((kb + 64,), GUARD, dtype=torch.uint8, device=dev),
-                          torch.full((n + 2,), -1, dtype=torch.int32, device=dev),
-                          torch.full((vb + 64,), GUARD, dtype=torch.uint8, device=dev),
-                          torch.full((n + 2,), -1, dtype=torch.int32, device=dev),
-                          torch.full((n + 1,), -1, dtype=torch.int64, device=dev), 0)
-
-
-def untouched(kv, offsets=True):
-    ok = bool((kv.keys == GUARD).all() and (kv.vals == GUARD).all() and (kv.ts == -1).all())
-    return ok and (not offsets or bool((kv.key_off == -1).all() and (kv.val_off == -1).all()))
-
-
-def all_empty(r, seg, nq):
-    assert (r["status"] == ln.EMPTY).all() and seg.tolist() == [0] * (nq + 1)
-    for f in ("sources", "raw", "merged", "n"):
-        assert (r[f] == 0).all(), f
 
 
 @pytest.mark.parametrize("mode", ln.MODES)
@@ -103,7 +48,7 @@ def test_every_field_and_byte_equals_the_expectation(name, bs, mode):
     rn, rkb, rvb = sizes_of(raw_runs)
     r, seg, raw, out, st = run(ss, view, c, range(len(c)), mode, (rn, rkb, rvb), (n, kb, vb))  # exact capacities
     assert st == [n, kb, vb, 0, rn, rkb, rvb, len(raw_runs)]
-    check_results(r, exp)
+    check_results(r, exp, ln.FIELDS)
     check_stream(out, out_rows, seg)
     check_stream(raw, raw_runs)
     assert (r["merged"] == r["raw"]).all()
@@ -160,17 +105,17 @@ def test_sizing_calls_and_the_capacity_contract():
     # no stream at all: the table scans' sizes
     r, seg, _, _, st = run(ss, view, c, sel, "view", None, None)
     assert st == [0, 0, 0, 0, rn, rkb, rvb, subs] and seg.tolist() == [0] * (nq + 1)
-    check_results(r, exp, fields=("sources", "raw"))
+    check_results(r, exp, ("sources", "raw"))
     assert (r["merged"] == 0).all() and (r["n"] == 0).all()
     # out = NULL: every size, res and seg_start
     r, seg, raw, out, st = run(ss, view, c, sel, "view", (rn, rkb, rvb), None)
     assert out is None and st == full and seg.tolist() == want_seg
-    check_results(r, exp)
+    check_results(r, exp, ln.FIELDS)
     check_stream(raw, raw_runs)
     # sub_cap one short: no scan runs
     raw, out = guarded(rn, rkb, rvb, dev), guarded(n, kb, vb, dev)
     r, seg, _, _, st = run(ss, view, c, sel, "view", (rn, rkb, rvb), (n, kb, vb), sub_cap=subs - 1, raw=raw, out=out)
-    assert st[3] == ERR_CAPACITY and st[7] == subs
+    assert st[3] == LSMBLK_ERR_CAPACITY and st[7] == subs
     all_empty(r, seg, nq)
     assert untouched(raw, offsets=False) and untouched(out, offsets=False)
     # a capacity of raw one short
@@ -179,8 +124,8 @@ def test_sizing_calls_and_the_capacity_contract():
         caps[short] -= 1
         raw, out = guarded(rn, rkb, rvb, dev), guarded(n, kb, vb, dev)
         r, seg, _, _, st = run(ss, view, c, sel, "view", tuple(caps), (n, kb, vb), raw=raw, out=out)
-        assert st == [0, 0, 0, ERR_CAPACITY, rn, rkb, rvb, subs] and seg.tolist() == [0] * (nq + 1), short
-        check_results(r, exp, fields=("sources", "raw"))
+        assert st == [0, 0, 0, LSMBLK_ERR_CAPACITY, rn, rkb, rvb, subs] and seg.tolist() == [0] * (nq + 1), short
+        check_results(r, exp, ("sources", "raw"))
         assert (r["merged"] == 0).all() and (r["n"] == 0).all() and (r["status"] == ln.EMPTY).all()
         assert untouched(raw), short
     # a capacity of out one short
@@ -189,8 +134,8 @@ def test_sizing_calls_and_the_capacity_contract():
         caps[short] -= 1
         raw, out = guarded(rn, rkb, rvb, dev), guarded(n, kb, vb, dev)
         r, seg, raw, _, st = run(ss, view, c, sel, "view", (rn, rkb, rvb), tuple(caps), raw=raw, out=out)
-        assert st == [n, kb, vb, ERR_CAPACITY, rn, rkb, rvb, subs] and seg.tolist() == want_seg, short
-        check_results(r, exp)
+        assert st == [n, kb, vb, LSMBLK_ERR_CAPACITY, rn, rkb, rvb, subs] and seg.tolist() == want_seg, short
+        check_results(r, exp, ln.FIELDS)
         assert untouched(out), short
         raw.n = rn
         check_stream(raw, raw_runs)
@@ -256,9 +201,9 @@ def test_a_malformed_block_empties_its_ranges_only():
     assert sum(rws[i]["n"] for i in clean) > 100 and all(rws[i]["raw"] > 0 for i in dirty)
     sel = clean + dirty
     r, seg, _, out, st = run(ss, view, c, sel, "view", (20000, 800000, 400000), (20000, 800000, 400000))
-    assert st[3] == ERR_MALFORMED
+    assert st[3] == LSMBLK_ERR_MALFORMED
     exp, out_rows, _ = ls.arrays([rws[i] for i in clean])
-    check_results(r[:len(clean)], exp)
+    check_results(r[:len(clean)], exp, ln.FIELDS)
     check_stream(out, out_rows + [[] for _ in dirty], seg)
     tail = r[len(clean):]
     assert (tail["status"] == ln.EMPTY).all() and all((tail[f] == 0).all() for f in ("sources", "raw", "merged", "n"))

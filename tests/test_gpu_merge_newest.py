@@ -14,6 +14,7 @@ import lsm_get_cases as lc
 import lsm_scan_cases as ls
 import lsm_scan_newest_cases as ln
 import merge_newest_cases as mn
+from gpu_kit import GUARD, _need_gpu, guarded, untouched  # noqa: F401 (_need_gpu: autouse)
 from lsm_amd import batch, shard, sst
 from lsm_amd._lib import (LSMBLK_E_CAPACITY, LSMBLK_E_INVAL, LSMBLK_E_MALFORMED, LSMBLK_GET_FOUND, LSMBLK_MERGE_RUNS,
                           LSMBLK_MERGE_TWO_LEVEL, LsmBlkError)
@@ -23,13 +24,6 @@ from test_gpu_compact import assert_kv_equal, dev_entries, kv_runs, to_dev
 
 pytestmark = pytest.mark.gpu
 NEWEST, RUNS, TWO = mn.NEWEST, LSMBLK_MERGE_RUNS, LSMBLK_MERGE_TWO_LEVEL
-GUARD = 0xAB
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a ROCm device")
 
 
 _cases = {}
@@ -111,14 +105,6 @@ def test_compaction_equals_the_oracle_over_the_newest_order_paths(name):
 
 
 # ---------------------------------------------------------------- capacity contract
-def guarded(n, kb, vb):
-    return batch.KVStream(torch.full((kb + 64,), GUARD, dtype=torch.uint8, device="cuda"),
-                          torch.full((n + 2,), -1, dtype=torch.int32, device="cuda"),
-                          torch.full((vb + 64,), GUARD, dtype=torch.uint8, device="cuda"),
-                          torch.full((n + 2,), -1, dtype=torch.int32, device="cuda"),
-                          torch.full((n + 1,), -1, dtype=torch.int64, device="cuda"), 0)
-
-
 def test_an_out_stream_one_short_reports_capacity_and_writes_nothing():
     case = cases()["key_ties"]
     d, n = to_dev(case.kv), case.kv.n
@@ -129,8 +115,7 @@ def test_an_out_stream_one_short_reports_capacity_and_writes_nothing():
         out = guarded(n, kb, vb)
         _, s = merge_raw(d, case.rs, NEWEST, out, tuple(caps))
         assert s == [n, kb, vb, s[3]] and batch._status(torch.tensor(s)) == LSMBLK_E_CAPACITY, (short, s)
-        assert bool((out.keys == GUARD).all() and (out.vals == GUARD).all() and (out.ts == -1).all()), short
-        assert bool((out.key_off == -1).all() and (out.val_off == -1).all()), short
+        assert untouched(out), short
     out = guarded(n, kb, vb)   # exactly enough
     _, s = merge_raw(d, case.rs, NEWEST, out, (n, kb, vb))
     assert s == [n, kb, vb, 0]

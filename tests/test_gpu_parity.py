@@ -9,17 +9,13 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_kit import _need_gpu  # noqa: F401 (autouse)
 from lsm_amd import batch, synth
-from lsm_amd._lib import LSMBLK_E_CAPACITY, LSMBLK_E_MALFORMED, LsmBlkError
+from lsm_amd._lib import (LSMBLK_DEBUG_DECODE_LAG, LSMBLK_DEBUG_DECODE_LAG_BYTES, LSMBLK_DEBUG_TWO_PASS_DECODE,
+                          LSMBLK_E_CAPACITY, LSMBLK_E_MALFORMED, LsmBlkError)
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a ROCm device")
 
 
 def to_dev(kv: O.KV):
@@ -665,11 +661,11 @@ def test_verifying_decode_counts_in_the_crc_pass(gen, n, bs, mode):
     block that breaks the decode rules under a correct checksum."""
     from lsm_amd._lib import LSMBLK_E_MALFORMED, lib
     ctx = batch._ctx(0)
-    assert lib().lsmblk_debug_set(ctx, 3, int(mode == "two_pass")) == 0
+    assert lib().lsmblk_debug_set(ctx, LSMBLK_DEBUG_TWO_PASS_DECODE, int(mode == "two_pass")) == 0
     try:
         _verifying_decode_counts(gen, n, bs)
     finally:
-        lib().lsmblk_debug_set(ctx, 3, 0)
+        lib().lsmblk_debug_set(ctx, LSMBLK_DEBUG_TWO_PASS_DECODE, 0)
 
 
 def _verifying_decode_counts(gen, n, bs):
@@ -714,11 +710,11 @@ def test_decode_modes(cfg, n, mode):
     assert rc == 0
     ctx = batch._ctx(0)
     if mode == "two_pass":
-        assert lib().lsmblk_debug_set(ctx, 3, 1) == 0
+        assert lib().lsmblk_debug_set(ctx, LSMBLK_DEBUG_TWO_PASS_DECODE, 1) == 0
     elif mode == "lag_bytes":
-        assert lib().lsmblk_debug_set(ctx, 6, 300 * 4096) == 0
+        assert lib().lsmblk_debug_set(ctx, LSMBLK_DEBUG_DECODE_LAG_BYTES, 300 * 4096) == 0
     else:
-        assert lib().lsmblk_debug_set(ctx, 4, 128 if mode == "lag128" else 1 << 20) == 0
+        assert lib().lsmblk_debug_set(ctx, LSMBLK_DEBUG_DECODE_LAG, 128 if mode == "lag128" else 1 << 20) == 0
     try:
         for shift in (0, 5):
             db, do = dev_blocks(ref_blocks, ref_off, shift)
@@ -728,18 +724,18 @@ def test_decode_modes(cfg, n, mode):
                   for i in range(len(ref_off) - 1)]
         np.testing.assert_array_equal(ent.cpu().numpy().view(np.uint64), np.concatenate([[0], np.cumsum(counts)]))
     finally:
-        lib().lsmblk_debug_set(ctx, 3, 0)
-        lib().lsmblk_debug_set(ctx, 4, 0)
+        lib().lsmblk_debug_set(ctx, LSMBLK_DEBUG_TWO_PASS_DECODE, 0)
+        lib().lsmblk_debug_set(ctx, LSMBLK_DEBUG_DECODE_LAG, 0)
 
 
 def test_decode_lag_setting_bounds():
     """Lags below two tiles or above 2^24 blocks are refused."""
     from lsm_amd._lib import lib
     ctx = batch._ctx(0)
-    assert lib().lsmblk_debug_set(ctx, 4, 127) != 0
-    assert lib().lsmblk_debug_set(ctx, 4, (1 << 24) + 1) != 0
-    assert lib().lsmblk_debug_set(ctx, 4, 10240) == 0
-    assert lib().lsmblk_debug_set(ctx, 4, 0) == 0  # the default (scaled by the block size)
+    assert lib().lsmblk_debug_set(ctx, LSMBLK_DEBUG_DECODE_LAG, 127) != 0
+    assert lib().lsmblk_debug_set(ctx, LSMBLK_DEBUG_DECODE_LAG, (1 << 24) + 1) != 0
+    assert lib().lsmblk_debug_set(ctx, LSMBLK_DEBUG_DECODE_LAG, 10240) == 0
+    assert lib().lsmblk_debug_set(ctx, LSMBLK_DEBUG_DECODE_LAG, 0) == 0  # the default (scaled by the block size)
 
 
 @pytest.mark.parametrize("cfg,n,seg_bytes", [("U", 400_000, 2 << 20), ("Z", 400_000, 2 << 20), ("U", 200_000, 64 << 10),

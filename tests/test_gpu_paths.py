@@ -12,17 +12,13 @@ import pytest
 import torch
 
 import path_cases as pc
+from gpu_kit import _need_gpu  # noqa: F401 (autouse)
 from lsm_amd import batch, synth
+from lsm_amd._lib import LSMBLK_DEBUG_DECODE_LAG, LSMBLK_DEBUG_TWO_PASS_DECODE
 from oracle import oracle as O
 from test_gpu_parity import assert_kv_equal, dev_blocks, framed_check, framed_want, slot_check, to_dev
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a ROCm device")
 
 
 def cu_count():
@@ -201,8 +197,8 @@ def test_decode_block_counts_on_tile_edges():
     ctx = batch._ctx(0)
     try:
         for mode in ("default", "lag128", "two_pass", "framed"):
-            assert lib().lsmblk_debug_set(ctx, 3, int(mode == "two_pass")) == 0
-            assert lib().lsmblk_debug_set(ctx, 4, 128 if mode == "lag128" else 0) == 0
+            assert lib().lsmblk_debug_set(ctx, LSMBLK_DEBUG_TWO_PASS_DECODE, int(mode == "two_pass")) == 0
+            assert lib().lsmblk_debug_set(ctx, LSMBLK_DEBUG_DECODE_LAG, 128 if mode == "lag128" else 0) == 0
             for nblk in TILE_EDGE_NBLK:
                 e, end = int(ent[nblk]), int(ref_off[nblk])
                 want = O.KV(ref_kv.keys[:ref_kv.key_off[e]], ref_kv.key_off[:e + 1], ref_kv.vals[:ref_kv.val_off[e]],
@@ -218,5 +214,5 @@ def test_decode_block_counts_on_tile_edges():
                 assert_kv_equal(got, want)
                 np.testing.assert_array_equal(gent.cpu().numpy(), ent[:nblk + 1], err_msg=f"{mode}, {nblk} blocks")
     finally:
-        lib().lsmblk_debug_set(ctx, 3, 0)
-        lib().lsmblk_debug_set(ctx, 4, 0)
+        lib().lsmblk_debug_set(ctx, LSMBLK_DEBUG_TWO_PASS_DECODE, 0)
+        lib().lsmblk_debug_set(ctx, LSMBLK_DEBUG_DECODE_LAG, 0)

@@ -11,7 +11,8 @@ import subprocess
 import sys
 
 import pytest
-import torch
+
+from gpu_kit import _need_gpu  # noqa: F401 (autouse)
 
 pytestmark = pytest.mark.gpu
 
@@ -23,10 +24,9 @@ import numpy as np
 import torch
 sys.path.insert(0, %(root)r)
 from lsm_amd import batch, shard, synth
-from lsm_amd._lib import lib, LsmBlkError
+from lsm_amd._lib import lib, LsmBlkError, LSMBLK_DEBUG_ROT_POISON as POISON
 from oracle import oracle as O
 
-POISON = 7  # LSMBLK_DEBUG_ROT_POISON
 out = {}
 keys, ko, vals, vo, ts, rs = synth.gen_runs(30000, nrun=3, seed=5, versions=2, tombstone=0.05)
 kv = O.KV(keys, ko, vals, vo, ts)
@@ -60,12 +60,6 @@ print(json.dumps(out))
 """
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a ROCm device")
-
-
 def test_corrupt_rotation_levels_report_internal_not_hang():
     from lsm_amd import _build
     from lsm_amd._lib import LSMBLK_E_INTERNAL
@@ -87,10 +81,9 @@ import numpy as np
 import torch
 sys.path.insert(0, %(root)r)
 from lsm_amd import batch, synth
-from lsm_amd._lib import lib, LsmBlkError
+from lsm_amd._lib import lib, LsmBlkError, LSMBLK_DEBUG_EMIT_POISON as POISON
 from oracle import oracle as O
 
-POISON = 10  # LSMBLK_DEBUG_EMIT_POISON
 out = {}
 kv = O.KV(*synth.gen_uniform(60000, seed=21))
 seg = [0, 20000, 40000, kv.n]

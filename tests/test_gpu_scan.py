@@ -11,55 +11,21 @@ import torch
 
 import get_cases as gc
 import scan_cases as sc
+from gpu_kit import (GUARD, _need_gpu, check_results, check_stream, guarded, opened_set, sizes_of, untouched)  # noqa: F401 (_need_gpu: autouse)
 from lsm_amd import batch, sst
-from lsm_amd._lib import LSMBLK_DEBUG_SCAN_UNITS, LsmBlkError, ScanResultC, lib
+from lsm_amd._lib import (LSMBLK_DEBUG_SCAN_UNITS, LSMBLK_ERR_CAPACITY, LSMBLK_ERR_EMPTY_KEY, LSMBLK_ERR_MALFORMED,
+                          LSMBLK_ERR_SEGMENTS, LsmBlkError, ScanResultC, lib)
 from oracle import pyref
 
 pytestmark = pytest.mark.gpu
 
-ERR_MALFORMED, ERR_CAPACITY, ERR_SEGMENTS, ERR_EMPTY_KEY = 1, 2, 16, 64
-GUARD = 0xAB
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a ROCm device")
-
-
-_sets = {}
-
 
 def opened(name):
-    if name not in _sets:
-        c = sc.case(name)
-        _sets[name] = sst.SstSet(c.files, c.file_off)
-    return _sets[name]
+    return opened_set(sc.case(name), ("scan", name))
 
 
 def flags_of(no_filter, mvcc):
     return (1 if no_filter else 0) | (2 if mvcc else 0)
-
-
-def sizes_of(rows):
-    kb, ko, vb, vo, ts, seg = sc.stream_of(rows)
-    return len(ts), len(kb), len(vb)
-
-
-def check_results(r, exp, sel=None):
-    for f in sc.FIELDS:
-        want = exp[f] if sel is None else exp[f][sel]
-        bad = np.nonzero(r[f].astype(np.uint64) != want)[0]
-        assert not len(bad), (f, bad[:5], r[f][bad[:5]], want[bad[:5]])
-
-
-def check_stream(kv, seg, rows):
-    kb, ko, vb, vo, ts, want_seg = sc.stream_of(rows)
-    assert seg.tolist() == want_seg.tolist()
-    assert kv.n == len(ts)
-    gk, gko, gv, gvo, gts = kv.to_numpy()
-    assert gko.tolist() == ko.tolist() and gvo.tolist() == vo.tolist() and gts.tolist() == ts.tolist()
-    assert gk.tobytes() == kb and gv.tobytes() == vb
 
 
 def run(ss, c, sel, flags, caps):
@@ -75,8 +41,8 @@ def test_scan_equals_expectation(name, no_filter, mvcc):
     n, kb, vb = sizes_of(rows)
     r, seg, kv, st = run(ss, c, range(len(c)), flags_of(no_filter, mvcc), (n, kb, vb))
     assert st == [n, kb, vb, 0]
-    check_results(r, exp)
-    check_stream(kv, seg, rows)
+    check_results(r, exp, sc.FIELDS)
+    check_stream(kv, rows, seg)
 
 
 @pytest.mark.parametrize("name", ("bs256", "threshold"))
@@ -87,21 +53,16 @@ def test_sizing_call_and_capacity_contract(name):
     want_seg = sc.stream_of(rows)[5].tolist()
     r, seg, kv, st = run(ss, c, range(len(c)), 0, None)  # out = NULL: the sizes, res and seg_start
     assert kv is None and st == [n, kb, vb, 0] and seg.tolist() == want_seg
-    check_results(r, exp)
+    check_results(r, exp, sc.FIELDS)
     dev = ss.device
     for short in range(3):  # one entry / key byte / value byte short
         caps = [n, kb, vb]
         caps[short] -= 1
-        out = batch.KVStream(torch.full((kb + 64,), GUARD, dtype=torch.uint8, device=dev),
-                             torch.full((n + 2,), -1, dtype=torch.int32, device=dev),
-                             torch.full((vb + 64,), GUARD, dtype=torch.uint8, device=dev),
-                             torch.full((n + 2,), -1, dtype=torch.int32, device=dev),
-                             torch.full((n + 1,), -1, dtype=torch.int64, device=dev), 0)
+        out = guarded(n, kb, vb, dev)
         r, seg, _, st = ss.scan_raw(c.q_sst, c.lower, c.upper, c.lkind, c.ukind, 0, tuple(caps), out)
-        assert st == [n, kb, vb, ERR_CAPACITY] and seg.tolist() == want_seg
-        check_results(r, exp)
-        assert (out.keys == GUARD).all() and (out.vals == GUARD).all()
-        assert (out.key_off == -1).all() and (out.val_off == -1).all() and (out.ts == -1).all()
+        assert st == [n, kb, vb, LSMBLK_ERR_CAPACITY] and seg.tolist() == want_seg
+        check_results(r, exp, sc.FIELDS)
+        assert untouched(out)
     # exactly enough: the guard bytes after the arenas stay
     out = batch.KVStream(torch.full((kb + 64,), GUARD, dtype=torch.uint8, device=dev),
                          torch.zeros(n + 1, dtype=torch.int32, device=dev),
@@ -110,7 +71,7 @@ def test_sizing_call_and_capacity_contract(name):
                          torch.zeros(n + 1, dtype=torch.int64, device=dev), 0)
     r, seg, kv, st = ss.scan_raw(c.q_sst, c.lower, c.upper, c.lkind, c.ukind, 0, (n, kb, vb), out)
     assert st == [n, kb, vb, 0]
-    check_stream(kv, seg, rows)
+    check_stream(kv, rows, seg)
     assert (out.keys[kb:] == GUARD).all() and (out.vals[vb:] == GUARD).all()
     with pytest.raises(LsmBlkError):
         bad = list(c.q_sst)
@@ -157,8 +118,8 @@ def test_every_placement_of_arenas_and_query_keys():
         torch.cuda.synchronize()
         assert stats.tolist() == [n, kb, vb, 0]
         out.n = n
-        check_stream(out, seg.cpu().numpy().view(np.uint32), rows)
-        check_results(res.cpu().numpy().view(np.dtype(ScanResultC)), exp, sel)
+        check_stream(out, rows, seg.cpu().numpy().view(np.uint32))
+        check_results(res.cpu().numpy().view(np.dtype(ScanResultC)), exp, sc.FIELDS, sel)
         assert (keys[:ko] == GUARD).all() and (keys[ko + kb:] == GUARD).all()
         assert (vals[:vo] == GUARD).all() and (vals[vo + vb:] == GUARD).all()
 
@@ -190,8 +151,8 @@ def test_query_counts_and_blocks_per_unit(nq, budget):
     finally:
         assert lib().lsmblk_debug_set(h, LSMBLK_DEBUG_SCAN_UNITS, 0) == 0
     assert st == list(sizes_of(rows)) + [0]
-    check_results(r, exp, sel)
-    check_stream(kv, seg, rows)
+    check_results(r, exp, sc.FIELDS, sel)
+    check_stream(kv, rows, seg)
 
 
 def test_degenerate_inputs():
@@ -210,8 +171,8 @@ def test_degenerate_inputs():
     rows = [r_ if o else [] for r_, o in zip(rows, other)]
     r, seg, kv, st = broken.scan_raw(c.q_sst, c.lower, c.upper, c.lkind, c.ukind, 0, sizes_of(rows))
     assert st == list(sizes_of(rows)) + [0]
-    check_stream(kv, seg, rows)
-    check_results(r[other], exp, other)
+    check_stream(kv, rows, seg)
+    check_results(r[other], exp, sc.FIELDS, other)
     assert (r["status"][~other] == sc.EMPTY).all() and (r["n"][~other] == 0).all()
     assert all((r[f][~other] == sc.NONE).all() for f in ("blk0", "ent0", "blk1", "ent1"))
     # q_sst >= nsst and an empty bounded key: flagged, those ranges empty, the others answered
@@ -219,11 +180,11 @@ def test_degenerate_inputs():
     k0, k1 = s0.entries[5][0], s0.entries[40][0]
     want = sc.scan_one(s0, 1, k0, 1, k1, False, False)
     r, seg, kv, st = ss.scan_raw([0, 9, 0], [k0, k0, k0], [k1, k1, k1], 1, 1, 0, (1000, 8000, 30000))
-    assert st[3] == ERR_SEGMENTS and r["n"].tolist() == [want["n"], 0, want["n"]] and r["blk0"][1] == sc.NONE
-    check_stream(kv, seg, [want["entries"], [], want["entries"]])
+    assert st[3] == LSMBLK_ERR_SEGMENTS and r["n"].tolist() == [want["n"], 0, want["n"]] and r["blk0"][1] == sc.NONE
+    check_stream(kv, [want["entries"], [], want["entries"]], seg)
     r, seg, kv, st = ss.scan_raw([0, 0, 0, 0], [k0, b"", k0, b""], [k1, k1, b"", b""], [1, 2, 1, 0], [1, 1, 2, 0], 0,
                                  (4000, 30000, 90000))
-    assert st[3] == ERR_EMPTY_KEY and r["status"].tolist() == [sc.OK, sc.EMPTY, sc.EMPTY, sc.OK]
+    assert st[3] == LSMBLK_ERR_EMPTY_KEY and r["status"].tolist() == [sc.OK, sc.EMPTY, sc.EMPTY, sc.OK]
     assert r["n"].tolist() == [want["n"], 0, 0, len(s0.entries)]
 
 
@@ -248,10 +209,10 @@ def test_a_malformed_block_empties_its_ranges_only():
     dirty = [i for i in sel if exp["n"][i] and exp["blk0"][i] < victim < exp["blk1"][i]]
     assert clean and dirty
     r, seg, kv, st = run(ss, c, clean + dirty, 3, (200000, 2000000, 6000000))
-    assert st[3] == ERR_MALFORMED
-    check_results(r[:len(clean)], exp, clean)
+    assert st[3] == LSMBLK_ERR_MALFORMED
+    check_results(r[:len(clean)], exp, sc.FIELDS, clean)
     assert (r["status"][len(clean):] == sc.EMPTY).all() and (r["n"][len(clean):] == 0).all()
-    check_stream(kv, seg, [rows[i] for i in clean] + [[] for _ in dirty])
+    check_stream(kv, [rows[i] for i in clean] + [[] for _ in dirty], seg)
 
 
 @pytest.mark.parametrize("name", ("bs128", "threshold", "ties"))
@@ -299,9 +260,9 @@ def test_read_filter_over_scan_output(name):
     out, oseg, st = filtered(kv, seg, ts, sizes_of(want))
     assert st == list(sizes_of(want)) + [0]
     out.n = st[0]
-    check_stream(out, oseg, want)
+    check_stream(out, want, oseg)
     got, gseg = batch.read_filter(kv, seg, ts)
-    check_stream(got, gseg, want)
+    check_stream(got, want, gseg)
 
 
 def test_read_filter_capacity_contract():
@@ -315,15 +276,10 @@ def test_read_filter_capacity_contract():
     for short in range(3):
         caps = [n, kb, vb]
         caps[short] -= 1
-        out = batch.KVStream(torch.full((kb + 64,), GUARD, dtype=torch.uint8, device=dev),
-                             torch.full((n + 2,), -1, dtype=torch.int32, device=dev),
-                             torch.full((vb + 64,), GUARD, dtype=torch.uint8, device=dev),
-                             torch.full((n + 2,), -1, dtype=torch.int32, device=dev),
-                             torch.full((n + 1,), -1, dtype=torch.int64, device=dev), 0)
+        out = guarded(n, kb, vb, dev)
         _, oseg, st = filtered(kv, seg, ts, tuple(caps), out)
-        assert st == [n, kb, vb, ERR_CAPACITY]
-        assert (out.keys == GUARD).all() and (out.vals == GUARD).all() and (out.ts == -1).all()
-        assert (out.key_off == -1).all() and (out.val_off == -1).all()
+        assert st == [n, kb, vb, LSMBLK_ERR_CAPACITY]
+        assert untouched(out)
     out = batch.KVStream(torch.full((kb + 64,), GUARD, dtype=torch.uint8, device=dev)[5:],
                          torch.zeros(n + 1, dtype=torch.int32, device=dev),
                          torch.full((vb + 64,), GUARD, dtype=torch.uint8, device=dev)[11:],
@@ -332,13 +288,13 @@ def test_read_filter_capacity_contract():
     _, oseg, st = filtered(kv, seg, ts, (n, kb, vb), out)
     assert st == [n, kb, vb, 0]
     out.n = n
-    check_stream(out, oseg, want)
+    check_stream(out, want, oseg)
     assert (out.keys[kb:] == GUARD).all() and (out.vals[vb:] == GUARD).all()
     # a decreasing segment table is refused
     bad = seg.copy()
     bad[3], bad[4] = bad[4] + 1, bad[3]
     _, _, st = filtered(kv, bad, ts, (n, kb, vb))
-    assert st[3] & ERR_SEGMENTS
+    assert st[3] & LSMBLK_ERR_SEGMENTS
 
 
 def test_read_filter_segment_boundaries_and_long_version_runs():
@@ -359,14 +315,14 @@ def test_read_filter_segment_boundaries_and_long_version_runs():
     out, oseg, st = filtered(kv, seg, ts, sizes_of(want))
     assert st == list(sizes_of(want)) + [0]
     out.n = st[0]
-    check_stream(out, oseg, want)
+    check_stream(out, want, oseg)
     # a tombstone as the newest visible version hides the key; read_ts below every version: nothing
     for t in (0, nver // 2, nver // 2 + 1, nver + 100):
         w = [sc.lsm_iterate(long_key, t)]
         kv1, seg1 = kv_of([long_key])
         out, oseg, st = filtered(kv1, seg1, [t], (2, 16, 16))
         out.n = st[0]
-        check_stream(out, oseg, w)
+        check_stream(out, w, oseg)
     out, oseg, st = filtered(*kv_of([[]]), [1], (2, 16, 16))  # an empty stream
     assert st == [0, 0, 0, 0] and oseg.tolist() == [0, 0]
 
@@ -396,7 +352,7 @@ def test_scan_merge_read_filter_equals_lsm_iterator_over_merge_iterator():
             want = sc.lsm_iterate(merged, read_ts, (uk, up))
             r, seg, kv, st = ss.scan_raw([0, 1], [lo, lo], [up, up], lk, uk, 2 if mvcc else 0, sizes_of(runs))
             assert st[3] == 0
-            check_stream(kv, seg, runs)
+            check_stream(kv, runs, seg)
             m = batch.merge_runs(kv, seg)
             got, gseg = batch.read_filter(m, [0, m.n], read_ts)
-            check_stream(got, gseg, [want])
+            check_stream(got, [want], gseg)

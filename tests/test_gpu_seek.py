@@ -6,17 +6,12 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_kit import _need_gpu  # noqa: F401 (autouse)
 from lsm_amd import batch, synth
 from lsm_amd._lib import LsmBlkError
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a ROCm device")
 
 
 def blocks_of(seed, versions, bs=4096, nkeys=3000):

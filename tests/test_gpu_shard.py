@@ -8,16 +8,11 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_kit import _need_gpu  # noqa: F401 (autouse)
 from lsm_amd import batch, shard, synth
 from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a ROCm device")
 
 
 def case(seed, versions=1, nkeys=6000, nrun=5, tomb=0.05):

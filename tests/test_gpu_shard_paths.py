@@ -7,8 +7,6 @@ rules, and the range predicate lo <= key < hi on its edges in every merge mode. 
 branch runs is chosen here, not by a seed."""
 import ctypes
 import dataclasses
-import os
-import re
 import time
 
 import numpy as np
@@ -17,23 +15,14 @@ import torch
 
 import path_cases as pc
 import shard_cases as sc
+from gpu_kit import _need_gpu  # noqa: F401 (autouse)
 from lsm_amd import batch, shard
-from lsm_amd._lib import LSMBLK_E_INVAL, LsmBlkError
+from lsm_amd._lib import LSMBLK_ERR_CAPACITY, LSMBLK_ERR_SEGMENTS, LSMBLK_E_INVAL, LsmBlkError
 from oracle import oracle as O
 from test_gpu_compact import dev_entries, to_dev
 
 pytestmark = pytest.mark.gpu
 RUNS, TWO, NEWEST = sc.RUNS, sc.TWO, sc.NEWEST
-
-with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "lsmblk.h")) as _f:
-    _H = _f.read()
-ERR_CAPACITY, ERR_SEGMENTS = (int(re.search(r"#define LSMBLK_ERR_%s (\d+)u" % n, _H).group(1)) for n in ("CAPACITY", "SEGMENTS"))
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a ROCm device")
 
 
 _memo = {}
@@ -167,7 +156,7 @@ def test_segments_is_reported(name):
     The same ext with LAST is valid and equals the oracle."""
     case, p, d0 = sc.error_cases()[name]
     r = Range(case).prepare()
-    check_refused(r, p, d0, ERR_SEGMENTS)
+    check_refused(r, p, d0, LSMBLK_ERR_SEGMENTS)
     check_good_call(r.ctx)
     if name != "m_inside_versions":
         last = dataclasses.replace(case, last=True)
@@ -192,7 +181,7 @@ def test_sst_cap_covers_the_range_or_capacity_is_reported(c):
             assert check_point(case, p, d0, got, answers[(case.name, p, d0)]) == c + 1
             outcome[cap] = "ok"
         else:
-            assert got[1][3] == ERR_CAPACITY and got[1][:3] == [0, 0, 0] and got[5] == b"", (cap, got[1])
+            assert got[1][3] == LSMBLK_ERR_CAPACITY and got[1][:3] == [0, 0, 0] and got[5] == b"", (cap, got[1])
             outcome[cap] = "capacity"
             check_good_call(ctx)
         if 2 ** sc.shard_flevels(cap) < c:
@@ -213,7 +202,7 @@ def test_seg_cap_one_short_reports_capacity():
     assert nseg >= 5
     assert check_point(case, p, d0, r.run(carry_in(p, d0), seg_cap=nseg + 1)) == nseg
     cout, s, seg_got, _, _, blocks = r.run(carry_in(p, d0), seg_cap=nseg)
-    assert s[3] == ERR_CAPACITY and s[:3] == [0, 0, 0] and blocks == b"", s
+    assert s[3] == LSMBLK_ERR_CAPACITY and s[:3] == [0, 0, 0] and blocks == b"", s
     assert (seg_got[:nseg] == case.m + p_out).all() and (seg_got[nseg:] == 0xFFFFFFFF).all(), seg_got[:nseg + 2]
     assert check_point(case, p, d0, r.run(carry_in(p, d0))) == nseg   # (the carry clears the report)
     check_good_call(r.ctx)

@@ -17,6 +17,7 @@ import torch
 
 import get_cases as gc
 import open_cases as oc
+from gpu_kit import _need_gpu  # noqa: F401 (autouse)
 from lsm_amd import batch, sst
 from lsm_amd._lib import SstDescC, SstIndexC
 from oracle import pyref
@@ -27,12 +28,6 @@ GUARD = 4096          # bytes before the files' view and after the last file
 PAT_DESC, PAT_INDEX = 0xC7, 0x5B
 DESC_B, INDEX_B = ctypes.sizeof(SstDescC), ctypes.sizeof(SstIndexC)
 PAD_REC = 2           # pattern records before and after desc / index
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a ROCm device")
 
 
 @pytest.fixture(scope="module")

@@ -16,6 +16,7 @@ import pytest
 import torch
 
 import sst_cases as sc
+from gpu_kit import _need_gpu  # noqa: F401 (autouse)
 from lsm_amd import batch
 from lsm_amd import sst as S
 from lsm_amd._lib import LSMBLK_E_CAPACITY
@@ -25,12 +26,6 @@ from test_gpu_parity import dev_blocks, to_dev
 from test_gpu_paths import rehome
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a ROCm device")
 
 
 def run_files(case, lay, d=None, nsst=None):

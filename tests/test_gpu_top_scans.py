@@ -28,8 +28,9 @@ import get_cases as gc
 import path_cases as pc
 import scan_cases as scc
 import sst_cases as sc
+from gpu_kit import _need_gpu  # noqa: F401 (autouse)
 from lsm_amd import batch, sst
-from lsm_amd._lib import lib
+from lsm_amd._lib import LSMBLK_DEBUG_TWO_PASS_DECODE, LSMBLK_ERR_MALFORMED, lib
 from oracle import oracle as O
 from oracle import pyref
 from test_gpu_get import corrupt, opened
@@ -40,13 +41,6 @@ pytestmark = pytest.mark.gpu
 
 WG = scc.kScanWg  # threads of a scan workgroup (static_assert in lsmblk_get.hip: == kWgScan)
 kTile = pc.read_constants(pc._SRC, ("kTile",))["kTile"]
-ERR_MALFORMED = 1
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a ROCm device")
 
 
 # ------------------------------------------------------------------------------- val_scan_kernel
@@ -79,8 +73,8 @@ def test_open_of_1025_ssts_one_malformed():
     bufs[bad] = corrupt("bloom-offset-past-file", bufs[bad])
     off = [0] + np.cumsum([len(b) for b in bufs]).tolist()
     ss = sst.SstSet(b"".join(bufs), off)
-    assert ss.err.tolist() == [ERR_MALFORMED if s == bad else 0 for s in range(nsst)]
-    assert ss.open_stats == [nsst - 1, nsst - 1, ERR_MALFORMED, 0]
+    assert ss.err.tolist() == [LSMBLK_ERR_MALFORMED if s == bad else 0 for s in range(nsst)]
+    assert ss.open_stats == [nsst - 1, nsst - 1, LSMBLK_ERR_MALFORMED, 0]
     good = [s for s in range(nsst) if s != bad]
     assert [int(ss.desc["blk0"][s]) for s in good] == list(range(nsst - 1))
     for s in good:
@@ -117,11 +111,11 @@ def test_two_pass_decode_scan_shares(one_entry_blocks, extra):
     want = O.KV(ref.keys[:ref.key_off[nblk]], ref.key_off[:nblk + 1], ref.vals[:ref.val_off[nblk]],
                 ref.val_off[:nblk + 1], ref.ts[:nblk])
     ctx = batch._ctx(0)
-    assert lib().lsmblk_debug_set(ctx, 3, 1) == 0
+    assert lib().lsmblk_debug_set(ctx, LSMBLK_DEBUG_TWO_PASS_DECODE, 1) == 0
     try:
         got, ent = batch.decode_blocks(*dev_blocks(blocks[:int(off[nblk])], off[:nblk + 1]), with_blk_ent=True)
     finally:
-        lib().lsmblk_debug_set(ctx, 3, 0)
+        lib().lsmblk_debug_set(ctx, LSMBLK_DEBUG_TWO_PASS_DECODE, 0)
     assert_kv_equal(got, want)
     np.testing.assert_array_equal(ent.cpu().numpy(), np.arange(nblk + 1))
 

@@ -11,21 +11,14 @@ import pytest
 import torch
 
 import walk_cases as wc
+from gpu_kit import _need_gpu  # noqa: F401 (autouse)
 from lsm_amd import batch
-from lsm_amd._lib import lib
+from lsm_amd._lib import LSMBLK_DEBUG_PLAN_PIPE, lib
 from oracle import oracle as O
 from test_gpu_parity import framed_check, slot_check, to_dev
 from test_gpu_paths import decode_check, packed_check, rehome
 
 pytestmark = pytest.mark.gpu
-
-LSMBLK_DEBUG_PLAN_PIPE = 9  # include/lsmblk.h
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _need_gpu():
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need a ROCm device")
 
 
 def cu_count():

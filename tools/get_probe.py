@@ -30,7 +30,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lsm_amd import batch, sst  # noqa: E402
 from lsm_amd._build import src_sha  # noqa: E402
-from lsm_amd._lib import LSMBLK_GET_NO_FILTER, GetResultC, kernel_log, lib  # noqa: E402
+from lsm_amd._lib import LSMBLK_GET_NO_FILTER, GetResultC, kernel_timing  # noqa: E402
 
 KLEN, VLEN, ENTRY = 16, 100, 4 + 10 + 8 + 2 + 100 + 2  # ~ bytes per entry in a block (6 key bytes shared)
 LINES = []
@@ -142,15 +142,13 @@ def main():
 
     step("per-kernel times", 120)
     ctx = batch._ctx(dev.index)
-    lib().lsmblk_debug_set(ctx, 2, 1)  # LSMBLK_DEBUG_KERNEL_TIMING
-    kernel_log(ctx)
-    for _ in range(3):
-        ss._open(cap)
-        run(0, True)
-        run(LSMBLK_GET_NO_FILTER)
-    torch.cuda.synchronize()
+    with kernel_timing(ctx) as kl:
+        for _ in range(3):
+            ss._open(cap)
+            run(0, True)
+            run(LSMBLK_GET_NO_FILTER)
     emit(what="kernels", note="ms per launch; sst_get_kernel averages one default and one no_filter launch",
-         **{k: round(ms / ln, 4) for k, (ln, ms) in kernel_log(ctx).items()})
+         **{k: round(ms / ln, 4) for k, (ln, ms) in kl.items()})
 
     # ---- the composition that existed before: host filters and block search, then lsmblk_seek_batch
     nb = min(a.base_queries, nq)
@@ -181,20 +179,18 @@ def main():
          seek_blocks_ms=round((t2 - t1) * 1e3, 1), mlookups_per_s=round(nb / (t2 - t0) / 1e6, 4))
     step("baseline: seek_blocks alone", 300)
     qb_all = [base[bs[i]] + tabs[bs[i]].find_block_idx(bkeys[i]) for i in range(nb)]
-    kernel_log(ctx)
     walls = []
-    for _ in range(5):
-        t0 = time.perf_counter()
-        idx = batch.seek_blocks(files, blk_off, qb_all, bkeys, tail=4)
-        walls.append((time.perf_counter() - t0) * 1e3)
-    kl = kernel_log(ctx)
+    with kernel_timing(ctx) as kl:
+        for _ in range(5):
+            t0 = time.perf_counter()
+            idx = batch.seek_blocks(files, blk_off, qb_all, bkeys, tail=4)
+            walls.append((time.perf_counter() - t0) * 1e3)
     seek_ms = kl["seek_kernel"][1] / kl["seek_kernel"][0]
     # the same lookups through the new kernel, timed the same way (kernel log)
     sub = lambda t, k: t[:k].contiguous()
-    for _ in range(5):
-        ss.get_into(sub(qs, nb), qk, sub(qo, nb + 1), sub(qt, nb), nb, LSMBLK_GET_NO_FILTER, res, stats)
-    torch.cuda.synchronize()
-    kl = kernel_log(ctx)
+    with kernel_timing(ctx) as kl:
+        for _ in range(5):
+            ss.get_into(sub(qs, nb), qk, sub(qo, nb + 1), sub(qt, nb), nb, LSMBLK_GET_NO_FILTER, res, stats)
     get_ms = kl["sst_get_kernel"][1] / kl["sst_get_kernel"][0]
     # landings: seek_blocks' entry index (+ the spill) against no_filter's (blk, ent)
     bad = 0

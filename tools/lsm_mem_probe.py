@@ -42,7 +42,7 @@ from get_probe import ENTRY, KLEN, VLEN, key_bytes, spread, timed  # noqa: E402
 from lsm_amd import batch, sst  # noqa: E402
 from lsm_amd._build import src_sha  # noqa: E402
 from lsm_amd._lib import (LSMBLK_GET_MVCC, LSMBLK_LSM_SCAN_STATS_WORDS, LSMBLK_SCAN_MVCC, GetResultC, LsmGetResultC,  # noqa: E402
-                          LsmScanResultC, kernel_log, lib)
+                          LsmScanResultC, kernel_timing)
 
 NL0, NLEVEL, PER_LEVEL, NMEM = 4, 3, 4, 4
 C = NL0 + NLEVEL
@@ -182,21 +182,16 @@ class Scan:
     def call(self):
         self.run()
         torch.cuda.synchronize()
-        return [int(x) & 0xFFFFFFFFFFFFFFFF for x in self.stats.cpu().tolist()]
+        return batch._stats_words(self.stats)
 
 
 def kernel_ms(ctx, fn, calls=5):
     """ms per launch of every kernel of `calls` calls of fn (a pass of its own, after a warm-up call)."""
     fn()
-    torch.cuda.synchronize()
-    lib().lsmblk_debug_set(ctx, 2, 1)  # LSMBLK_DEBUG_KERNEL_TIMING
-    kernel_log(ctx)
-    for _ in range(calls):
-        fn()
-    torch.cuda.synchronize()
-    out = {k: round(ms / ln, 4) for k, (ln, ms) in kernel_log(ctx).items()}
-    lib().lsmblk_debug_set(ctx, 2, 0)
-    return out
+    with kernel_timing(ctx) as log:
+        for _ in range(calls):
+            fn()
+    return {k: round(ms / ln, 4) for k, (ln, ms) in log.items()}
 
 
 def leg_nmem0(a, dev, rng, ctx):

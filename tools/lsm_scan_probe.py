@@ -42,7 +42,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from get_probe import ENTRY, KLEN, VLEN, key_bytes, spread  # noqa: E402
 from lsm_amd import batch, sst  # noqa: E402
 from lsm_amd._build import src_sha  # noqa: E402
-from lsm_amd._lib import LSMBLK_LSM_SCAN_STATS_WORDS, LsmScanResultC, ScanResultC, kernel_log, lib  # noqa: E402
+from lsm_amd._lib import LSMBLK_LSM_SCAN_STATS_WORDS, LsmScanResultC, ScanResultC, kernel_timing  # noqa: E402
 
 INCL_EXCL = 1 | (2 << 2)
 MODE_FLAGS = {"default": 0, "mvcc": 2, "newest": 4}  # LSMBLK_SCAN_MVCC, LSMBLK_LSM_SCAN_NEWEST
@@ -133,7 +133,7 @@ class LsmScan:
     def call(self):
         self.run()
         torch.cuda.synchronize()
-        return [int(x) & 0xFFFFFFFFFFFFFFFF for x in self.stats.cpu().tolist()]
+        return batch._stats_words(self.stats)
 
 
 def composition(s, lo_id, hi_id, caps):
@@ -180,13 +180,10 @@ def composition(s, lo_id, hi_id, caps):
 
 def kernel_times(ctx, scan, calls=3):
     """ms per launch of every kernel of `calls` calls (LSMBLK_DEBUG_KERNEL_TIMING, a pass of its own)."""
-    lib().lsmblk_debug_set(ctx, 2, 1)
-    kernel_log(ctx)
-    for _ in range(calls):
-        scan.call()
-    kern = {k: ms_ / ln for k, (ln, ms_) in kernel_log(ctx).items()}
-    lib().lsmblk_debug_set(ctx, 2, 0)
-    return kern
+    with kernel_timing(ctx) as log:
+        for _ in range(calls):
+            scan.call()
+    return {k: ms_ / ln for k, (ln, ms_) in log.items()}
 
 
 def mode_legs(ctx, s, lo_id, hi_id, modes, runs, want):
@@ -235,12 +232,7 @@ def main():
     med = sorted(ms)[len(ms) // 2]
     out_bytes = st[1] + st[2] + 16 * st[0]
     step("lsm_scan: per-kernel times", 120)
-    lib().lsmblk_debug_set(ctx, 2, 1)  # LSMBLK_DEBUG_KERNEL_TIMING
-    kernel_log(ctx)
-    for _ in range(3):
-        new.call()
-    kern = {k: round(ms_ / ln, 4) for k, (ln, ms_) in kernel_log(ctx).items()}
-    lib().lsmblk_debug_set(ctx, 2, 0)
+    kern = {k: round(v, 4) for k, v in kernel_times(ctx, new).items()}
     line["view"] = dict(ssts=s.nsst, sst_mib=a.sst_mib, l0=s.nl0, levels=s.nlevel, tables_per_level=s.per_level)
     line["lsm_scan"] = dict(ranges=a.ranges, span=a.span, table_scans=st[7], raw_entries=st[4], out_entries=st[0],
                             out_bytes=out_bytes, ranges_per_s=round(a.ranges / med * 1e3), out_gb_per_s=round(out_bytes / med / 1e6, 3),
@@ -267,12 +259,7 @@ def main():
     lo_id, hi_id = s.ranges(a.rank_ranges, 16, rng)
     step("rank70: lsm_scan and its kernel log", 300)
     new = LsmScan(s, lo_id, hi_id)
-    lib().lsmblk_debug_set(ctx, 2, 1)
-    kernel_log(ctx)
-    for _ in range(3):
-        new.call()
-    kern = {k: ms_ / ln for k, (ln, ms_) in kernel_log(ctx).items()}
-    lib().lsmblk_debug_set(ctx, 2, 0)
+    kern = kernel_times(ctx, new)
     rk, raw = kern["lsm_scan_rank_kernel"], new.st[4]
     line["rank70"] = dict(ranges=a.rank_ranges, runs_per_range=70, raw_entries=raw, rank_kernel_ms=round(rk, 4),
                           entries_per_s=round(raw / rk * 1e3), searches_per_s=round(raw * 69 / rk * 1e3),

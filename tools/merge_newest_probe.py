@@ -26,7 +26,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from lsm_amd import _lib, batch, synth  # noqa: E402
-from lsm_amd._lib import check, kernel_log, lib  # noqa: E402
+from lsm_amd._lib import kernel_log, kernel_timing  # noqa: E402
 
 MODES = {"runs": getattr(_lib, "LSMBLK_MERGE_RUNS", 0), "newest": getattr(_lib, "LSMBLK_MERGE_NEWEST", 2)}
 TILE_KERNELS = ("merge_tile_kernel", "merge_big_kernel")
@@ -77,14 +77,12 @@ def main():
         s = buf.stats.cpu().tolist()
         if s[3]:
             sys.exit(f"merge_newest_probe: mode {name} failed with error flags {s[3]}")
-        check(lib().lsmblk_debug_set(ctx, 2, 1))  # LSMBLK_DEBUG_KERNEL_TIMING
-        kernel_log(ctx)  # empties the log
         reps = []
-        for _ in range(a.reps):
-            batch.compact_into(kv, rt, a.runs, opts, buf)
-            torch.cuda.synchronize(dev)
-            reps.append({k: ms for k, (_, ms) in kernel_log(ctx).items()})
-        check(lib().lsmblk_debug_set(ctx, 2, 0))
+        with kernel_timing(ctx):
+            for _ in range(a.reps):  # (the log is read, and so emptied, per repetition)
+                batch.compact_into(kv, rt, a.runs, opts, buf)
+                torch.cuda.synchronize(dev)
+                reps.append({k: ms for k, (_, ms) in kernel_log(ctx).items()})
         names = sorted(set().union(*reps))
         line["modes"][name] = dict(
             merged=s[4], kept=s[5], blocks=s[0], ssts=s[2],

@@ -15,7 +15,8 @@ os.environ.setdefault("LSMBLK_SO_OVERRIDE", os.path.join(os.path.dirname(os.path
 import torch  # noqa: E402
 
 from lsm_amd import batch, synth  # noqa: E402
-from lsm_amd._lib import check, lib  # noqa: E402
+from lsm_amd._lib import (LSMBLK_DEBUG_DECODE_LAG, LSMBLK_DEBUG_DECODE_SKIP,  # noqa: E402
+                          LSMBLK_DEBUG_TWO_PASS_DECODE, check, lib)
 
 
 def main():
@@ -26,17 +27,17 @@ def main():
     seg = synth.segments_by_bytes(key_off, val_off)
     blocks, blk_off = batch.encode_kv(kv, seg, synth.BLOCK_SIZE["U"])
     ctx = batch._ctx(0)
-    check(lib().lsmblk_debug_set(ctx, 1, mask))
-    check(lib().lsmblk_debug_set(ctx, 3, int(os.environ.get("PROBE_TWO_PASS", "0"))))  # two-pass decode (A/B)
+    check(lib().lsmblk_debug_set(ctx, LSMBLK_DEBUG_DECODE_SKIP, mask))
+    check(lib().lsmblk_debug_set(ctx, LSMBLK_DEBUG_TWO_PASS_DECODE, int(os.environ.get("PROBE_TWO_PASS", "0"))))  # two-pass decode (A/B)
     if os.environ.get("PROBE_LAG"):
-        check(lib().lsmblk_debug_set(ctx, 4, int(os.environ["PROBE_LAG"])))
+        check(lib().lsmblk_debug_set(ctx, LSMBLK_DEBUG_DECODE_LAG, int(os.environ["PROBE_LAG"])))
     for _ in range(3):
         if which == "encode":
             batch.encode_kv(kv, seg, synth.BLOCK_SIZE["U"])
         else:
             batch.decode_blocks(blocks, blk_off)
     torch.cuda.synchronize()
-    check(lib().lsmblk_debug_set(ctx, 1, 0))
+    check(lib().lsmblk_debug_set(ctx, LSMBLK_DEBUG_DECODE_SKIP, 0))
     print(which, mask, "blocks", blk_off.numel() - 1)
 
 

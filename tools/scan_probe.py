@@ -38,7 +38,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lsm_amd import batch, sst  # noqa: E402
 from lsm_amd._build import src_sha  # noqa: E402
-from lsm_amd._lib import ScanResultC, kernel_log, lib  # noqa: E402
+from lsm_amd._lib import ScanResultC, kernel_timing  # noqa: E402
 from tools.get_probe import ENTRY, KLEN, VLEN, key_bytes, spread, timed  # noqa: E402
 
 LINES = []
@@ -143,14 +143,10 @@ def main():
         assert fstats.cpu().tolist() == [ne, kb, vb, 0], fstats
         emit(what="scan+filter", batch=name, ranges=nq, kept=ne, **spread(ms))
         step(f"{name}: per-kernel times", 120)
-        lib().lsmblk_debug_set(ctx, 2, 1)  # LSMBLK_DEBUG_KERNEL_TIMING
-        kernel_log(ctx)
-        for _ in range(3):
-            scan_filter()
-        torch.cuda.synchronize()
-        emit(what="kernels", batch=name, note="ms per launch",
-             **{k: round(ms_ / ln, 4) for k, (ln, ms_) in kernel_log(ctx).items()})
-        lib().lsmblk_debug_set(ctx, 2, 0)
+        with kernel_timing(ctx) as kl:
+            for _ in range(3):
+                scan_filter()
+        emit(what="kernels", batch=name, note="ms per launch", **{k: round(ms_ / ln, 4) for k, (ln, ms_) in kl.items()})
 
         # ---- the parent's composition on the first ranges of the batch
         nb = min(a.base, nq)
